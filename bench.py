@@ -72,6 +72,52 @@ REFERENCE_TRIANGULATION_CPU = dict(value=1000 / 130.7, unit="tracks/s", cores=8,
                                           "container (BASELINE.md section 2): 130.7 s = 131 ms per track")
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def caller_outputs(prob, valid_idx, deleted, shared, cam_type, fin):
+    """The arrays ``ba.bundle_adjustment`` hands its caller for the problem's current state, unpacked the same way: cameras
+    back in input-frame order, points in track order (rows of the valid tracks, deleted ones zero), per-frame K and the
+    radial parameter; plus the summary's initial / final cost.  -> {name: float64 numpy array}."""
+    S = int(prob.cam_q.shape[0])
+    ext = torch.cat([BA.quat_to_rotmat(prob.cam_q), prob.cam_t[:, :, None]], -1)
+    inv_perm = None
+    if prob.cam_perm is not None:
+        inv_perm = torch.empty_like(prob.cam_perm)
+        inv_perm[prob.cam_perm] = torch.arange(S, device=prob.cam_perm.device)
+        ext = ext[inv_perm]
+    pts = prob.pts.clone()
+    pts[deleted] = 0.0
+    pts = pts[torch.argsort(valid_idx)]                 # (the identity unless the problem numbers its points by track length)
+    idx = torch.zeros(S, dtype=torch.long, device=pts.device) if shared else \
+        (torch.arange(S, device=pts.device) if inv_perm is None else inv_perm)
+    K = torch.zeros((S, 3, 3), dtype=torch.float64, device=pts.device)
+    K[:, 0, 0] = K[:, 1, 1] = prob.intr[idx, 0]
+    K[:, 0, 2] = prob.intr[idx, 1]
+    K[:, 1, 2] = prob.intr[idx, 2]
+    K[:, 2, 2] = 1.0
+    out = {"points3D": pts, "extrinsics": ext, "intrinsics": K}
+    if cam_type == "SIMPLE_RADIAL":
+        out["extra_params"] = prob.intr[idx, 3][:, None]
+    out = {k: v.double().cpu().numpy() for k, v in out.items()}
+    out["cost"] = np.array([fin["initial_cost"], fin["final_cost"]], dtype=np.float64)
+    return out
+
+
+def dump_outputs(arrays, directory, max_bytes=DUMP_MAX_BYTES):
+    """Write {name: array} as directory/<name>.npy.  An array that does not fit the remaining budget is replaced by a fixed
+    sample of its rows (seeded, sorted: the same rows in every run of the same shape)."""
+    os.makedirs(directory, exist_ok=True)
+    left = max_bytes - 4096 * len(arrays)               # (room for the .npy headers)
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        if a.nbytes > left:
+            keep = left // a[0].nbytes
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+            name = f"{name}_sample"
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 def D(x, dev):
     return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
@@ -308,7 +354,13 @@ def main():
     ap.add_argument("--split-exchange", action="store_true",
                     help="opt-in, N > 1: exchange the reduced system in two parts, the off-diagonal tile launch's share on the "
                          "communicator's stream beside the diagonal launch (dist.SPLIT_EXCHANGE, DESIGN.md section 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the state after the last step, as "
+                         "ba.bundle_adjustment returns it: points3D, extrinsics, intrinsics, extra_params, cost) as "
+                         "DIR/<name>.npy in float64; at N > 1 rank 0 writes its shard")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.overlap:
         BA.OVERLAP_FACTORIZATION = True
     if args.split_exchange:
@@ -345,6 +397,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    books = {}      # id(problem) -> (valid_idx, deleted) of compile_problem: what --dump-outputs unpacks the points with
+
     def build(workload, solo=False):
         """-> (problem, numpy scene or None, initial cameras / points on the host or None).  solo: the whole problem on
         this rank alone (no collective at set-up)."""
@@ -355,18 +409,21 @@ def main():
             n_local = N // world if (workload in STRONG and not solo) else N
             sc = make_scene_device(S, n_local, cam_type, shared_camera=shared, seed=0, track_seed=1000 + rank, device=dev)
             ext0_c, K0_c, extra0_c, _ = perturb_for_ba(sc_cameras_only(sc), seed=0)
-            prob, _, _ = BA.compile_problem(sc.points3D_init, D(ext0_c, dev), D(K0_c, dev), sc.tracks, sc.mask, D(extra0_c, dev),
-                                            shared, cam_type, overlap=(world == 1 and args.overlap),
-                                            camera_split=not args.no_camera_split, adjacency_reduce=reduce_adj,
-                                            sort_points=BA.SORT_POINTS)   # (what the public entry, ba.bundle_adjustment, does)
+            prob, valid_idx, deleted = BA.compile_problem(sc.points3D_init, D(ext0_c, dev), D(K0_c, dev), sc.tracks, sc.mask,
+                                                          D(extra0_c, dev), shared, cam_type, overlap=(world == 1 and args.overlap),
+                                                          camera_split=not args.no_camera_split, adjacency_reduce=reduce_adj,
+                                                          sort_points=BA.SORT_POINTS)   # (what the public entry, ba.bundle_adjustment, does)
+            books[id(prob)] = (valid_idx, deleted)
             return prob, None, (sc, D(ext0_c, dev), D(K0_c, dev), D(extra0_c, dev))
         sc = make_scene(S, N, cam_type, shared_camera=shared, seed=0, track_seed=1000 + rank, full_visibility=(workload == "c3dense"))
         _, _, _, pts0 = perturb_for_ba(sc, seed=rank)
         ext0_c, K0_c, extra0_c, _ = perturb_for_ba(sc, seed=0)          # cameras identical on every rank
-        prob, _, _ = BA.compile_problem(D(pts0, dev), D(ext0_c, dev), D(K0_c, dev), D(sc.tracks, dev), D(sc.mask, dev),
-                                        D(extra0_c, dev), shared, cam_type, overlap=(world == 1 and args.overlap),
-                                        camera_split=not args.no_camera_split, adjacency_reduce=reduce_adj,
-                                            sort_points=BA.SORT_POINTS)   # (what the public entry, ba.bundle_adjustment, does)
+        prob, valid_idx, deleted = BA.compile_problem(D(pts0, dev), D(ext0_c, dev), D(K0_c, dev), D(sc.tracks, dev),
+                                                      D(sc.mask, dev), D(extra0_c, dev), shared, cam_type,
+                                                      overlap=(world == 1 and args.overlap),
+                                                      camera_split=not args.no_camera_split, adjacency_reduce=reduce_adj,
+                                                      sort_points=BA.SORT_POINTS)   # (what the public entry, ba.bundle_adjustment, does)
+        books[id(prob)] = (valid_idx, deleted)
         return prob, sc, (pts0, ext0_c, K0_c, extra0_c)
 
     def timed(prob, steps, warmup, profile, solo=False):
@@ -450,6 +507,9 @@ def main():
     # of 1684 us per LM iteration of configs[2] were gaps next to the seven observed launches, none between the others), so
     # observing inside the region made it 3 % slower than the work it times.  `ms_per_step_with_events` is the second pass.
     dt, fin, _ = timed(prob, args.steps, args.warmup, False)
+    if args.dump_outputs and rank == 0:
+        # (before the profiled pass below, which goes on from this state)
+        dump_outputs(caller_outputs(prob, *books[id(prob)], shared, cam_type, fin), args.dump_outputs)
     dt_events, _, prof = timed(prob, args.steps, 0, True)
     # ---- N > 1 with the strong problem as the main one: weak-scaling leg on configs[2] shards
     weak = None

@@ -2,17 +2,16 @@
 vggsfm_amd/{models,utils,two_view_geo} that has a namesake in the same-named module of the reference must accept every call
 the reference's own call sites can make -- the reference's parameter names, in the reference's order, with the reference's
 defaults, as a PREFIX of ours; anything we add must be optional.  Compared on the syntax trees (nothing of the reference is
-imported or executed).  Build container only: /root/reference does not exist on the GPU box."""
+imported or executed).  The reference's side -- parameter lists of its modules under models/utils/two_view_geo, and the
+keywords its call sites pass -- is recorded in tests/golden/reference_calls/boundary_signatures.npz (oracle/ref_replay.py:
+re-recorded by running this module with VGG_RECORD_REFERENCE=1 where the reference tree exists)."""
 import ast
 import os
 
-import pytest
+from oracle import ref_harness, ref_replay
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/vggsfm"
 PACKAGES = ("models", "utils", "two_view_geo")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 
 # Documented, deliberate differences (INTEGRATION.md section 6).  Key: "package/module.py:qualname".
 ALLOWED = {}
@@ -47,20 +46,57 @@ def _params(fn):
     return positional, kwonly, a.vararg is not None, a.kwarg is not None
 
 
-def _pairs():
+def _reference_side():
+    """What the reference's syntax trees say: {"signatures": {"pkg/module.py": {qualname: _params(...)}} for its modules under
+    PACKAGES, "call_sites": [[path, line, callee, [keywords]]] for every call anywhere in it whose callee (bare or attribute
+    name) is a public module-level function of those modules}."""
+    ref = os.path.join(ref_harness.REFERENCE_ROOT, "vggsfm")
+    signatures = {}
+    for pkg in PACKAGES:
+        for name in sorted(os.listdir(os.path.join(ref, pkg))):
+            if name.endswith(".py") and name != "__init__.py":
+                fns = _functions(os.path.join(ref, pkg, name))
+                signatures[f"{pkg}/{name}"] = {q: _params(fn) for q, fn in fns.items() if _public(q)}
+    callees = {q for sigs in signatures.values() for q in sigs if "." not in q}
+    sites = []
+    for dirpath, _, files in sorted(os.walk(ref)):
+        for f in sorted(files):
+            if not f.endswith(".py"):
+                continue
+            path = os.path.join(dirpath, f)
+            try:
+                tree = ast.parse(open(path).read())
+            except SyntaxError:
+                continue
+            for node in ast.walk(tree):
+                if not isinstance(node, ast.Call):
+                    continue
+                name = node.func.id if isinstance(node.func, ast.Name) else (
+                    node.func.attr if isinstance(node.func, ast.Attribute) else None)
+                if name in callees:
+                    sites.append([os.path.relpath(path, ref), node.lineno, name, [kw.arg for kw in node.keywords]])
+    return {"signatures": signatures, "call_sites": sites}
+
+
+def _reference():
+    side = ref_replay.calls("boundary_signatures").fn("vggsfm:<syntax trees>", _reference_side)()
+    as_params = lambda p: ([tuple(x) for x in p[0]], dict(p[1]), p[2], p[3])
+    return {rel: {q: as_params(p) for q, p in sigs.items()} for rel, sigs in side["signatures"].items()}, side["call_sites"]
+
+
+def _pairs(signatures):
     for pkg in PACKAGES:
         ours_dir = os.path.join(ROOT, "vggsfm_amd", pkg)
         for name in sorted(os.listdir(ours_dir)):
             if not name.endswith(".py") or name == "__init__.py":
                 continue
-            ref_path = os.path.join(REF, pkg, name)
-            if os.path.isfile(ref_path):
-                yield f"{pkg}/{name}", os.path.join(ours_dir, name), ref_path
+            if f"{pkg}/{name}" in signatures:
+                yield f"{pkg}/{name}", os.path.join(ours_dir, name), signatures[f"{pkg}/{name}"]
 
 
-def _compare(key, ours, ref):
-    """List of human-readable incompatibilities of `ours` against `ref` (both ast.FunctionDef)."""
-    (op, ok, ovar, okw), (rp, rk, rvar, rkw) = _params(ours), _params(ref)
+def _compare(key, ours, ref_params):
+    """List of human-readable incompatibilities of `ours` (ast.FunctionDef) against the reference's `_params`."""
+    (op, ok, ovar, okw), (rp, rk, rvar, rkw) = _params(ours), ref_params
     problems = []
     for i, (rname, rdef) in enumerate(rp):
         if i >= len(op):
@@ -94,8 +130,9 @@ def _compare(key, ours, ref):
 
 def test_every_namesake_accepts_the_reference_call_signature():
     problems, compared = [], 0
-    for rel, ours_path, ref_path in _pairs():
-        ours, ref = _functions(ours_path), _functions(ref_path)
+    signatures, _ = _reference()
+    for rel, ours_path, ref in _pairs(signatures):
+        ours = _functions(ours_path)
         for q in sorted(set(ours) & set(ref)):
             if not _public(q):
                 continue
@@ -107,39 +144,26 @@ def test_every_namesake_accepts_the_reference_call_signature():
                 continue
             problems += found
     assert compared >= 30, f"only {compared} namesake functions found: did a package move?"
-    assert not problems, "boundary drift against /root/reference:\n  " + "\n  ".join(problems)
+    assert not problems, "boundary drift against the reference:\n  " + "\n  ".join(problems)
 
 
 def test_reference_call_sites_keywords_exist():
     """Every keyword a reference call site passes to one of the namesake functions (by bare or attribute name) exists here.
     Catches a dropped keyword even when the positional prefix still matches."""
     ours_by_name = {}
-    for rel, ours_path, ref_path in _pairs():
+    signatures, sites = _reference()
+    for rel, ours_path, ref in _pairs(signatures):
         for q, fn in _functions(ours_path).items():
-            if "." not in q and _public(q) and q in _functions(ref_path):
+            if "." not in q and _public(q) and q in ref:
                 ours_by_name.setdefault(q, []).append((rel, fn))
     missing = []
-    for dirpath, _, files in os.walk(REF):
-        for f in files:
-            if not f.endswith(".py"):
-                continue
-            path = os.path.join(dirpath, f)
-            try:
-                tree = ast.parse(open(path).read())
-            except SyntaxError:
-                continue
-            for node in ast.walk(tree):
-                if not isinstance(node, ast.Call):
-                    continue
-                name = node.func.id if isinstance(node.func, ast.Name) else (
-                    node.func.attr if isinstance(node.func, ast.Attribute) else None)
-                if name not in ours_by_name:
-                    continue
-                for rel, fn in ours_by_name[name]:
-                    pos, kwonly, _, has_kw = _params(fn)
-                    names = {n for n, _ in pos} | set(kwonly)
-                    for kw in node.keywords:
-                        if kw.arg is not None and kw.arg not in names and not has_kw:
-                            missing.append(f"{os.path.relpath(path, REF)}:{node.lineno} passes {name}({kw.arg}=...) "
-                                           f"which {rel} does not accept")
+    for path, line, name, keywords in sites:
+        if name not in ours_by_name:
+            continue
+        for rel, fn in ours_by_name[name]:
+            pos, kwonly, _, has_kw = _params(fn)
+            names = {n for n, _ in pos} | set(kwonly)
+            for kw in keywords:
+                if kw is not None and kw not in names and not has_kw:
+                    missing.append(f"{path}:{line} passes {name}({kw}=...) which {rel} does not accept")
     assert not missing, "\n".join(sorted(set(missing)))

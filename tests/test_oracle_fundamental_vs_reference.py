@@ -19,16 +19,15 @@ import pytest
 import torch
 
 from oracle import fundamental as Fd
-from oracle import ref_harness
+from oracle import ref_replay
 from tests.test_oracle_fundamental import two_view
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference tree not present (GPU box)")
+REF = ref_replay.calls("oracle_fundamental_vs_reference")
 
 
 def _reference_modules():
-    ref_harness.install()
-    import vggsfm.two_view_geo.fundamental as rf
-    import vggsfm.two_view_geo.utils as ru
+    rf = REF.module("vggsfm.two_view_geo.fundamental")
+    ru = REF.module("vggsfm.two_view_geo.utils")
 
     def to_h(p):
         return torch.cat([p, torch.ones_like(p[..., :1])], -1)
@@ -175,13 +174,12 @@ def test_preliminary_camera_helpers_match_reference():
     (vggsfm/two_view_geo/fundamental.py:186-212, essential.py:36-83 -- kornia's ``cross_product_matrix`` / ``eye_like``
     style helpers restated by the harness -- and estimate_preliminary.py:244-272)."""
     import torch
-    ref_harness.install()
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        from vggsfm.two_view_geo import essential as RE
-        from vggsfm.two_view_geo import estimate_preliminary as RP
-        from vggsfm.two_view_geo import fundamental as RF
+        RE = REF.module("vggsfm.two_view_geo.essential")
+        RP = REF.module("vggsfm.two_view_geo.estimate_preliminary")
+        RF = REF.module("vggsfm.two_view_geo.fundamental")
     from vggsfm_amd.two_view_geo import estimate_preliminary as P
     # kornia helpers the reference imports by name (stubbed by the harness): restated here
     RE.ones_like, RE.where, RE.stack = torch.ones_like, torch.where, torch.stack

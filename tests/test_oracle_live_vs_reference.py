@@ -1,19 +1,32 @@
-"""CPU, build container only (needs /root/reference; skipped on the GPU box): the numpy oracle (oracle/geometry.py) against
-the REFERENCE's own torch functions run LIVE on freshly seeded inputs -- shapes and seeds that no committed golden vector
-has seen -- for every function of the torch half of the path: project_3D_points, cam_from_img (undistortion),
-filter_all_points3D, triangulate_by_pair and triangulate_tracks (LO-RANSAC; the torch.randperm draws the reference makes
-are recorded and replayed).  Same comparisons and tolerances as tests/test_oracle_golden.py; what this adds is that the
-oracle is not fitted to the goldens."""
+"""CPU: the numpy oracle (oracle/geometry.py) against the REFERENCE's own torch functions on freshly seeded inputs -- shapes
+and seeds that no golden vector of tests/test_oracle_golden.py has seen -- for every function of the torch half of the
+path: project_3D_points, cam_from_img (undistortion), filter_all_points3D, triangulate_by_pair and triangulate_tracks
+(LO-RANSAC; the torch.randperm draws the reference makes are recorded and replayed).  The reference's results are the
+recorded calls of tests/golden/reference_calls/oracle_live_vs_reference.npz (oracle/ref_replay.py: re-recorded by running
+this module with VGG_RECORD_REFERENCE=1 where the reference tree exists).  Same comparisons and tolerances as
+tests/test_oracle_golden.py; what this adds is that the oracle is not fitted to the goldens."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import geometry as G
-from oracle import ref_harness
+from oracle import ref_replay
 from oracle.gen_golden import T, _RecordRandperm, _StableSort, tc
 from vggsfm_amd.scene import make_scene, perturb_for_ba
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference tree not present (GPU box)")
+REF = ref_replay.calls("oracle_live_vs_reference")
+helpers = REF.module("vggsfm.utils.triangulation_helpers")
+tri = REF.module("vggsfm.utils.triangulation")
+
+
+def _triangulate_tracks_recording_draws(*args, **kwargs):
+    """The reference's triangulate_tracks under a stable sort, with the torch.randperm draws it makes."""
+    with _StableSort(), _RecordRandperm() as rec:
+        out = ref_replay.reference("vggsfm.utils.triangulation:triangulate_tracks")(*args, **kwargs)
+    return out, rec.draws
+
+
+triangulate_tracks_with_draws = REF.fn("vggsfm.utils.triangulation:triangulate_tracks", _triangulate_tracks_recording_draws)
 
 CASES = [  # seed, S, N, camera, shared
     (101, 7, 90, "SIMPLE_PINHOLE", False),
@@ -30,7 +43,6 @@ def _scene(seed, S, N, cam, shared):
 
 @pytest.mark.parametrize("seed,S,N,cam,shared", CASES)
 def test_projection_normalisation_and_filter_live(seed, S, N, cam, shared):
-    _, helpers, _ = ref_harness.load()
     sc, ext, K, extra, pts = _scene(seed, S, N, cam, shared)
     pts = pts.copy()
     pts[0] = [0.0, 0.0, -2.0]                                   # behind the cameras
@@ -54,7 +66,6 @@ def test_projection_normalisation_and_filter_live(seed, S, N, cam, shared):
 
 @pytest.mark.parametrize("seed,S,N,cam,shared", CASES)
 def test_triangulate_by_pair_live(seed, S, N, cam, shared):
-    tri, helpers, _ = ref_harness.load()
     sc, ext, K, extra, _ = _scene(seed, S, N, cam, shared)
     tn = helpers.cam_from_img(T(sc.tracks), T(K), T(extra))
     pr, cher, angr = tri.triangulate_by_pair(T(ext)[None], tn[None])
@@ -68,23 +79,21 @@ def test_triangulate_by_pair_live(seed, S, N, cam, shared):
 @pytest.mark.parametrize("seed,S,N,cam,iters", [(111, 9, 80, "SIMPLE_PINHOLE", 256), (112, 26, 60, "SIMPLE_RADIAL", 256),
                                                (113, 25, 50, "SIMPLE_PINHOLE", 128)])
 def test_triangulate_tracks_live(seed, S, N, cam, iters):
-    tri, helpers, _ = ref_harness.load()
     sc, ext, K, extra, _ = _scene(seed, S, N, cam, cam == "SIMPLE_RADIAL")
     vis, score = sc.vis.copy(), sc.score.copy()
     score[:, ::11] = 0.45                                        # whole tracks below the score threshold
     vis[1, ::7] = 0.04                                           # entries below the visibility threshold
     tn = helpers.cam_from_img(T(sc.tracks), T(K), T(extra))
     torch.manual_seed(seed)
-    with _StableSort(), _RecordRandperm() as rec:
-        pr, numr, mskr = tri.triangulate_tracks(T(ext), tc(tn), max_ransac_iters=iters, track_vis=tc(T(vis)),
-                                                track_score=tc(T(score)))
+    (pr, numr, mskr), draws = triangulate_tracks_with_draws(T(ext), tc(tn), max_ransac_iters=iters, track_vis=tc(T(vis)),
+                                                            track_score=tc(T(score)))
     comb = G.generate_combinations(S)
     if iters > len(comb):
-        assert not rec.draws
+        assert not draws
         pairs = comb
     else:
-        assert len(rec.draws) == 1                               # one chunk, one draw
-        pairs = comb[rec.draws[0][:iters]]
+        assert len(draws) == 1                                   # one chunk, one draw
+        pairs = comb[draws[0][:iters]]
     p, num, msk = G.triangulate_tracks_chunk(ext, tn.numpy(), pairs, lo_num=min(50, len(pairs)), track_vis=vis,
                                              track_score=score)
     assert np.array_equal(num, numr.numpy())
@@ -101,7 +110,6 @@ def test_reference_rejects_nonfinite_rays(bad):
     PRECONDITION of ``triangulate_tracks``; the drop-in raises the same exception type up front
     (vggsfm_amd/utils/triangulation.py), and the kernel's behaviour on such input is defined anyway (every RANSAC hypothesis of
     the track poisoned: tests/test_gpu_triangulation.py::test_nonfinite_ray_in_invisible_view)."""
-    tri, helpers, _ = ref_harness.load()
     seed, S, N = 117, 12, 90
     sc, ext, K, extra, _ = _scene(seed, S, N, "SIMPLE_PINHOLE", False)
     vis = sc.vis.copy()

@@ -5,17 +5,16 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref_harness
+from oracle import ref_replay
 from vggsfm_amd import video as V
 from vggsfm_amd.runners import generate_grid_samples, sample_subrange
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference tree not present (GPU box)")
+REF = ref_replay.calls("reference_helpers")
 
 
 def test_sample_subrange_and_grid_match_reference():
-    ref_harness.install()
-    from vggsfm.utils.utils import generate_grid_samples as ref_grid
-    from vggsfm.utils.utils import sample_subrange as ref_sub
+    ref_grid = REF.fn("vggsfm.utils.utils:generate_grid_samples")
+    ref_sub = REF.fn("vggsfm.utils.utils:sample_subrange")
     for N in range(1, 40):
         for L in range(1, 45):
             for idx in range(N):
@@ -37,9 +36,8 @@ def _rand_rot(n, g):
 def test_camera_alignment_matches_reference():
     """Own derivation (polar factor + one-dimensional least squares, video.py) against the reference's functions: the same
     similarity to rounding (float64)."""
-    ref_harness.install()
-    from vggsfm.utils.align import align_camera_extrinsics as ref_align
-    from vggsfm.utils.align import apply_transformation as ref_apply
+    ref_align = REF.fn("vggsfm.utils.align:align_camera_extrinsics")
+    ref_apply = REF.fn("vggsfm.utils.align:apply_transformation")
     g = torch.Generator().manual_seed(0)
     for n in (2, 9, 17, 33):
         src = torch.cat([_rand_rot(n, g), torch.randn(n, 3, 1, generator=g, dtype=torch.float64)], -1)
@@ -63,9 +61,8 @@ def test_get_EFP_and_sample_features4d_match_reference():
     lookup) -- the two edge functions of the Triangulator drop-in."""
     import types
 
-    ref_harness.install()
-    from vggsfm.models.utils import get_EFP as ref_efp
-    from vggsfm.models.utils import sample_features4d as ref_sample
+    ref_efp = REF.fn("vggsfm.models.utils:get_EFP")
+    ref_sample = REF.fn("vggsfm.models.utils:sample_features4d")
     from vggsfm_amd.models.utils import get_EFP, sample_features4d
     g = torch.Generator().manual_seed(1)
     for S, size in ((7, (1024.0, 768.0)), (3, (512.0, 512.0))):
@@ -82,16 +79,14 @@ def test_get_EFP_and_sample_features4d_match_reference():
     assert torch.equal(ref_sample(img, co), sample_features4d(img, co))
 
 
-@pytest.mark.skipif(not ref_harness.available(), reason="reference tree not present (GPU box)")
 def test_average_camera_prediction_matches_reference():
     """vggsfm_amd.utils.utils.average_camera_prediction (torch ops, scipy's quaternion conventions restated) against the
     reference's own function (vggsfm/utils/utils.py:25-164, scipy on the host) with the same fake predictor."""
     import types
     import warnings
-    ref_harness.install()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        from vggsfm.utils import utils as RU
+        RU = REF.module("vggsfm.utils.utils")
     from scipy.spatial.transform import Rotation
     from vggsfm_amd.utils import utils as U
     S = 9
@@ -127,11 +122,10 @@ def test_small_driver_helpers_match_reference():
     """find_best_initial_pair (triangulator.py:442-476), get_valid_frame_mask (triangulation.py:1222-1242),
     create_intri_matrix and generate_combinations (triangulation_helpers.py:590-645): the host-side mirrors against the
     reference's own functions on random inputs, bit for bit."""
-    ref_harness.install()
-    from vggsfm.models.triangulator import find_best_initial_pair as ref_pair
-    from vggsfm.utils.triangulation import get_valid_frame_mask as ref_valid
-    from vggsfm.utils.triangulation_helpers import create_intri_matrix as ref_K
-    from vggsfm.utils.triangulation_helpers import generate_combinations as ref_comb
+    ref_pair = REF.fn("vggsfm.models.triangulator:find_best_initial_pair")
+    ref_valid = REF.fn("vggsfm.utils.triangulation:get_valid_frame_mask")
+    ref_K = REF.fn("vggsfm.utils.triangulation_helpers:create_intri_matrix")
+    ref_comb = REF.fn("vggsfm.utils.triangulation_helpers:generate_combinations")
     from vggsfm_amd.models.triangulator import find_best_initial_pair
     from vggsfm_amd.utils.triangulation import get_valid_frame_mask
     from vggsfm_amd.utils.triangulation_helpers import create_intri_matrix, generate_combinations
@@ -162,10 +156,9 @@ def test_small_driver_helpers_match_reference():
 def test_order_and_se3_helpers_match_reference():
     """calculate_index_mappings / switch_tensor_order (utils/utils.py:167-187), closed_form_inverse_OpenCV
     (utils/metric.py:233-268) against the reference's own functions."""
-    ref_harness.install()
-    from vggsfm.utils.metric import closed_form_inverse_OpenCV as ref_inv
-    from vggsfm.utils.utils import calculate_index_mappings as ref_map
-    from vggsfm.utils.utils import switch_tensor_order as ref_switch
+    ref_inv = REF.fn("vggsfm.utils.metric:closed_form_inverse_OpenCV")
+    ref_map = REF.fn("vggsfm.utils.utils:calculate_index_mappings")
+    ref_switch = REF.fn("vggsfm.utils.utils:switch_tensor_order")
     from vggsfm_amd.utils.utils import calculate_index_mappings, closed_form_inverse_OpenCV, switch_tensor_order
     g = torch.Generator().manual_seed(1)
     for S in (1, 2, 5, 9):
