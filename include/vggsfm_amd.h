@@ -388,6 +388,44 @@ int vgg_cholesky_solve_split(double* A, double* b, int n, int split_a, int split
 int vgg_cholesky_solve_envelope(double* A, double* b, int n, const int32_t* first_blk, void* workspace, int32_t* device_fail,
                                 void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dense depth alignment (the reference's dense_depth stage)
+ *   extract_sparse_depth_and_point_from_reconstruction   vggsfm/runners/runner.py:744-772
+ *   align_dense_depth_maps                                vggsfm/utils/utils.py:635-770
+ * All pointers are device memory.  Images are indexed 0 .. num_images-1 by the caller; ragged disparity maps live in
+ * one flat float32 buffer, image i at disp_off[i] with heights[i] x widths[i] pixels, row-major.
+ *
+ * Sparse depths: one row per observation, rows grouped by image by the caller (obs_image ascending; within an image the
+ * reference's point-major order).  xyz (P,3) point rows, obs_point / obs_image (O) int32, point_id (O) int64, pose (S,3,4)
+ * [R|t], cam (S,4) f, cx, cy, k (k = 0 for SIMPLE_PINHOLE).  Out: uvd (O,3) distorted pixel + depth, xyzid (O,4). */
+int vgg_sparse_depth(const double* xyz, const int32_t* obs_point, const int32_t* obs_image, const int64_t* point_id,
+                     const double* pose, const double* cam, long num_obs, double* uvd, double* xyzid, void* stream);
+/* Per-image RANSAC fit disparity ~ scale * (1 / depth) ... as scikit-learn 1.7's RANSACRegressor(LinearRegression(),
+ * min_samples=2, residual_threshold=median(1/depth)/30, max_trials, loss="squared_error"), one workgroup per image, all
+ * images in one launch.  uvd (O,3) grouped by image: image i owns rows obs_ptr[i] .. obs_ptr[i+1] (obs_ptr int64,
+ * num_images + 1).  draws (num_images, num_draws, 2) int32 indices into the image's kept rows (scikit-learn's recorded
+ * sample_without_replacement draws), or NULL: draws from a counter-based generator keyed by `seed`.
+ * Out per image: scale, shift (float32), n_trials, n_inliers, n_kept, status (0 ok, 1 no observation, 2 ill-posed
+ * (non-finite data or threshold <= 0), 3 no consensus set, 4 fewer than 2 kept rows, 5 draws exhausted, 6 draw out of
+ * range); per observation: kept (passed the bounds / positive-disparity filter), inlier (in the final consensus set).
+ * workspace: vgg_depth_align_workspace_bytes(num_obs) device bytes. */
+size_t vgg_depth_align_workspace_bytes(long num_obs);
+int vgg_depth_align(const float* disp, const int64_t* disp_off, const int32_t* heights, const int32_t* widths,
+                    const double* uvd, const int64_t* obs_ptr, int num_images, long num_obs, const int32_t* draws,
+                    int num_draws, unsigned long long seed, int max_trials, float* scale, float* shift, int32_t* n_trials,
+                    int32_t* n_inliers, int32_t* n_kept, int32_t* status, uint8_t* kept, uint8_t* inlier, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* In place on disp (numpy float32 semantics): nonzero d -> d * scale[i] + shift[i]; outside (0, 1e4] -> 0; depth (same
+ * layout, float32) = 1 / d where d != 0 (an infinite quotient -> 0), else 0.  max_pixels = max_i heights[i] * widths[i]. */
+int vgg_depth_apply(float* disp, float* depth, const int64_t* disp_off, const int32_t* heights, const int32_t* widths,
+                    int num_images, long max_pixels, const float* scale, const float* shift, void* stream);
+/* Back-projection of num_pixels valid pixels: pixels (N) int64 row-major index inside image pixel_image (N) int32;
+ * normalised point by COLMAP's iterative undistortion (per point), times depth, then inv_pose (S,3,4) = [R^T | -R^T t].
+ * Out xyz (N,3) float64. */
+int vgg_depth_unproject(const int64_t* pixels, const int32_t* pixel_image, long num_pixels, const float* depth,
+                        const int64_t* disp_off, const int32_t* widths, const double* cam, const double* inv_pose,
+                        double* xyz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,7 +97,8 @@ class Rotation3d:
     def __mul__(self, other):
         if isinstance(other, Rotation3d):
             return Rotation3d(self._R @ other._R)
-        return self._R @ _np(other)
+        p = _np(other)
+        return p @ self._R.T if p.ndim == 2 else self._R @ p          # (N,3) arrays row by row, as pycolmap
 
 
 class Rigid3d:
@@ -124,7 +125,10 @@ class Rigid3d:
         if isinstance(other, Rigid3d):
             return Rigid3d(Rotation3d(self.rotation._R @ other.rotation._R),
                            self.rotation._R @ other.translation + self.translation)
-        return self.rotation._R @ _np(other) + self.translation
+        p = _np(other)
+        if p.ndim == 2:                                                    # (N,3) arrays row by row, as pycolmap
+            return p @ self.rotation._R.T + self.translation
+        return self.rotation._R @ p + self.translation
 
 
 # ----------------------------------------------------------------------------------------------- camera

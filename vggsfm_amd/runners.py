@@ -34,6 +34,7 @@ class GeometryConfig:
     shift_point2d_to_original_res: bool = False
     max_ransac_iters: int = 4096
     lo_num: int = 300
+    visual_dense_point_cloud: bool = False
 
 
 def generate_grid_samples(rect, N=None, pixel_interval=None):
@@ -192,4 +193,42 @@ class GeometryRunner:
                            unproj_dense_points3D=None, valid_2D_mask=valid_2D_mask, pred_track=pred_track, pred_vis=pred_vis,
                            pred_score=pred_score, valid_tracks=valid_tracks, additional_points_dict=additional_points_dict,
                            preliminary_dict=preliminary_dict)
+        return predictions
+
+    # ------------------------------------------------------------------ dense depth (runner.py:744-814)
+    def extract_sparse_depth_and_point_from_reconstruction(self, predictions):
+        """runner.py:744-772 with one projection kernel (vgg_sparse_depth) instead of the per-observation loop.  Sets
+        predictions["sparse_depth"] / ["sparse_point"]: per image name (in order of first appearance) an (n,3) array of
+        [u, v, depth] and an (n,4) array of [x, y, z, point3D_id], float64 (the reference keeps lists of 1-D arrays;
+        ``np.array`` of either is the same).  predictions["sparse_depth_device"] keeps the device-side result
+        (vggsfm_amd.dense_depth.SparseDepth) for ``dense_reconstruct``."""
+        from collections import defaultdict
+
+        from . import dense_depth as DD
+
+        sd = DD.sparse_depth(predictions["reconstruction"])
+        uvd, xyzid = sd.uvd.cpu().numpy(), sd.xyzid.cpu().numpy()
+        sparse_depth, sparse_point = defaultdict(list), defaultdict(list)
+        for k, name in enumerate(sd.names):
+            a, b = int(sd.obs_ptr[k]), int(sd.obs_ptr[k + 1])
+            sparse_depth[name] = uvd[a:b]
+            sparse_point[name] = xyzid[a:b]
+        predictions["sparse_depth"] = sparse_depth
+        predictions["sparse_point"] = sparse_point
+        predictions["sparse_depth_device"] = sd
+        return predictions
+
+    def dense_reconstruct(self, predictions, image_paths, original_images, disp_dict, samples=None, generator=None):
+        """runner.py:776-814 without the depth network: `disp_dict` holds the monocular disparity maps the caller's model
+        predicted (float32 (H, W) numpy arrays or device tensors, keyed by image name, as extract_dense_depth_maps returns
+        them); they are rescaled in place.  Sets predictions["depth_dict"] and ["unproj_dense_points3D"]
+        (cfg.visual_dense_point_cloud)."""
+        from .utils.utils import align_dense_depth_maps
+
+        depth_dict, unproj = align_dense_depth_maps(
+            predictions["reconstruction"], predictions["sparse_depth"], disp_dict, original_images,
+            visual_dense_point_cloud=bool(getattr(self.cfg, "visual_dense_point_cloud", False)), samples=samples,
+            generator=generator)
+        predictions["depth_dict"] = depth_dict
+        predictions["unproj_dense_points3D"] = unproj
         return predictions

@@ -1,4 +1,5 @@
-"""Camera-prediction averaging of the reference (vggsfm/utils/utils.py:25-187), as torch ops on the device.
+"""Camera-prediction averaging of the reference (vggsfm/utils/utils.py:25-187), as torch ops on the device, and its dense
+depth alignment (``align_dense_depth_maps``, utils.py:635-770) over the kernels of vggsfm_amd/dense_depth.py.
 
 ``average_camera_prediction`` runs the (learned, injected) camera predictor several times, each time with a different
 frame swapped to position 0, brings every prediction back to the frame order and to the gauge of frame 0, and averages:
@@ -13,6 +14,7 @@ runner.py:392-400) and by the video runner for every window (video_runner.py:662
 import random
 import types
 
+import numpy as np
 import torch
 
 
@@ -136,3 +138,72 @@ def camera_prior_from_predictor(camera_predictor, images):
                                          query_indices=[0, n // 2, n - 1])
         return torch.cat((cams.R, cams.T.unsqueeze(-1)), dim=-1)
     return prior
+
+
+def align_dense_depth_maps(reconstruction, sparse_depth, disp_dict, original_images, visual_dense_point_cloud=False,
+                           samples=None, generator=None, device=None):
+    """utils.py:635-770 on the device (vggsfm_amd/dense_depth.py, csrc/dense.hip): per key of `sparse_depth` (in its
+    order) the RANSAC fit disparity ~ scale * (1 / depth) + shift, then every map of `disp_dict` is rescaled IN PLACE,
+    validated to (0, 1e4] and inverted.  Returns (depth_dict, unproj_dense_points3D or None) like the reference, and raises
+    its ValueErrors -- after the maps of the images before the failing one were rescaled, as the reference's loop leaves
+    them.
+
+    disp_dict values: float32 (H, W) numpy arrays (depth_dict then holds numpy float32 maps) or float32 device tensors
+    (depth_dict holds device tensors, nothing is copied to the host except the dense cloud).  `samples`: recorded
+    scikit-learn draws, one (T, 2) index array per key (a sequence in key order or a dict by key), replayed exactly;
+    otherwise the draws come from a generator on the device seeded from `generator` (torch.Generator, int or None)."""
+    from .. import dense_depth as DD
+
+    names = list(sparse_depth)
+    if not names:
+        return {}, ({} if visual_dense_point_cloud else None)
+    dev = torch.device("cuda" if device is None else device)
+    uvds = [np.asarray(sparse_depth[n], dtype=np.float64).reshape(-1, 3) for n in names]
+    obs_ptr = np.concatenate([[0], np.cumsum([len(u) for u in uvds])]).astype(np.int64)
+    maps = [disp_dict[n] for n in names]
+    on_device = all(torch.is_tensor(m) for m in maps)
+    packed = DD.pack_maps(maps, dev)
+    uvd = torch.from_numpy(np.concatenate(uvds) if obs_ptr[-1] else np.zeros((0, 3))).to(dev)
+    if isinstance(samples, dict):
+        samples = [samples[n] for n in names]
+    if isinstance(generator, int):
+        seed = generator
+    else:
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item())
+    res = DD.align(packed, uvd, obs_ptr, samples=samples, seed=seed)
+    status = res.status.cpu().numpy()
+    bad = np.nonzero(status != 0)[0]
+    n_ok = int(bad[0]) if len(bad) else len(names)
+    depth = DD.apply(packed, res.scale, res.shift, n_ok)
+    off = packed.off.cpu().numpy()
+    depth_dict, cloud = {}, {}
+    if visual_dense_point_cloud and n_ok:
+        ids = {reconstruction.images[i].name: i for i in reconstruction.images}
+        img_ids = [ids[n] for n in names[:n_ok]]
+        pose, cam = DD._camera_rows(reconstruction, img_ids)
+        inv = [reconstruction.images[i].cam_from_world.inverse() for i in img_ids]     # [R^T | -R^T t] as Rigid3d
+        inv_pose = np.stack([np.concatenate([t.rotation.matrix(), t.translation[:, None]], axis=1) for t in inv])
+        xyz, counts = DD.unproject(packed, depth, cam, inv_pose, n_ok)
+        xyz = xyz.cpu().numpy()
+        cstart = np.concatenate([[0], np.cumsum(counts.cpu().numpy())])
+    flat_host = packed.flat.cpu() if not on_device else None
+    depth_host = depth.cpu() if not on_device else None
+    for k, n in enumerate(names[:n_ok]):
+        h, w = maps[k].shape
+        a, b = int(off[k]), int(off[k + 1])
+        if on_device:
+            maps[k].copy_(packed.flat[a:b].view(h, w))
+            depth_dict[n] = depth[a:b].view(h, w).clone()
+        else:
+            maps[k][...] = flat_host[a:b].numpy().reshape(h, w)
+            depth_dict[n] = depth_host[a:b].numpy().reshape(h, w).copy()
+        if visual_dense_point_cloud:
+            valid = (maps[k] != 0).reshape(-1)
+            valid = valid.cpu().numpy() if torch.is_tensor(valid) else valid
+            img = original_images[n]
+            img = img.cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
+            rgb = (img / 255.0).reshape(-1, 3)[valid]
+            cloud[n] = np.array([xyz[cstart[k]:cstart[k + 1]], rgb])
+    if len(bad):
+        DD.raise_for_status(status[bad[0]])
+    return depth_dict, (cloud if visual_dense_point_cloud else None)
