@@ -426,6 +426,49 @@ int vgg_depth_unproject(const int64_t* pixels, const int32_t* pixel_image, long 
                         const int64_t* disp_off, const int32_t* widths, const double* cam, const double* inv_pose,
                         double* xyz, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reprojection video (the reference's make_reproj_video stage)
+ *   create_video_with_reprojections   vggsfm/utils/utils.py:428-546
+ *   filter_invisible_reprojections    vggsfm/utils/utils.py:393-425
+ * All pointers are device memory.  color_mode: 0 dis_to_center, 1 dis_to_origin, 2 point_order.
+ *
+ * Colour statistics over all num_points (> 0) points of the model, float64 as numpy computes them, into
+ * stats[VGG_REPROJ_STATS]: [0..2] np.median(xyz, axis=0) (mode 0; else 0), [3] min_dis, [4] max_dis (mode 0: min and
+ * np.percentile(., 95) of the distances to the median; mode 1: min and max of the norms; mode 2: 0), [5] the largest point
+ * id (mode 2; else 0).  xyz (P,3) (modes 0, 1), point_id (P) int64 (mode 2).  Four launches, no host round trip.
+ * workspace: vgg_reproj_stats_workspace_bytes(num_points) device bytes. */
+#define VGG_REPROJ_STATS 8
+#define VGG_REPROJ_MAX_RADIUS 32
+size_t vgg_reproj_stats_workspace_bytes(long num_points);
+int vgg_reproj_stats(const double* xyz, const int64_t* point_id, long num_points, int color_mode, double* stats,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Centres, colours and per-pixel visibility of the observations of frames frame_begin .. frame_end-1.  Frame f owns the
+ * observation rows obs_range[2f] .. obs_range[2f+1] of uvd (O,3) [u, v, depth] and xyzid (O,4) [x, y, z, point id]
+ * (O < 2^31); its grid window, (heights[f] + 2r) x (widths[f] + 2r) cells with cell (gx, gy) = integer centre (gx - r,
+ * gy - r), starts at grid_off[f] - grid_off[frame_begin] (grid_off int64, prefix of the window sizes); chunk_cells =
+ * grid_off[frame_end] - grid_off[frame_begin] (< 2^31), max_frame_obs = the largest observation count of the chunk.
+ * Centre: rint(u), rint(v) (half to even).  An observation whose centre lies outside its window cannot touch its image and
+ * gets obs_cell = -1; in the window, the cell's winner is the smallest depth, ties to the lowest row, -0.0 == +0.0, a NaN
+ * depth first (np.argmin).  grid_key (uint64) / grid_obs (uint32) hold chunk_cells cells each and are overwritten (the
+ * winner's row, 0xffffffff where none).  Colour (when lut != NULL): matplotlib's Colormap.__call__ of the colour index
+ * (stats from vgg_reproj_stats), looked up in lut (lut_n + 3 entries: the colormap's N colours, under, over, bad; each
+ * int(255 * channel) as r | g << 8 | b << 16) into color (O).  Optional: centers (O,2) int32 (INT32_MIN outside the window),
+ * visible (O) uint8 (1 = drawn).  draw_radius <= VGG_REPROJ_MAX_RADIUS. */
+int vgg_reproj_visible(const double* uvd, const double* xyzid, const int64_t* obs_range, const int32_t* heights,
+                       const int32_t* widths, const int64_t* grid_off, int frame_begin, int frame_end, long max_frame_obs,
+                       long chunk_cells, int draw_radius, int color_mode, const double* stats, const uint32_t* lut,
+                       int lut_n, int32_t* obs_cell, uint32_t* color, int32_t* centers, uint8_t* visible,
+                       unsigned long long* grid_key, uint32_t* grid_obs, void* stream);
+/* Padded BGR canvases (frame_end - frame_begin, canvas_h, canvas_w, 3) uint8 into out, after vgg_reproj_visible on the same
+ * frames and grid: zero outside the centred image (top = (canvas_h - h) / 2, left = (canvas_w - w) / 2), inside it the
+ * RGB source pixel (images: flat uint8, frame f at img_off[f], heights[f] x widths[f] x 3) flipped to BGR, with every
+ * winning circle within draw_radius composited in row order: coverage k = the number of i, j in 0..3 with
+ * (8(x - cx) + 2i - 3)^2 + (8(y - cy) + 2j - 3)^2 <= 64 r^2 (r = 0: k = 16 at the centre), out = (old (16 - k) + c k + 8) >> 4
+ * per channel, colour channel 0 into canvas channel 0. */
+int vgg_reproj_draw(const uint8_t* images, const int64_t* img_off, const int32_t* heights, const int32_t* widths,
+                    const int64_t* grid_off, int frame_begin, int frame_end, int canvas_h, int canvas_w, int draw_radius,
+                    const uint32_t* grid_obs, const uint32_t* color, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

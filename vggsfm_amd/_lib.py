@@ -66,7 +66,8 @@ EXPORTED = ["vgg_build_arch", "vgg_abi_version", "vgg_abi_sizeof", "vgg_project_
             "vgg_ba_profile", "vgg_ba_profile_read", "vgg_cholesky_workspace_bytes", "vgg_pose_refine",
             "vgg_p3p_ransac_workspace_bytes", "vgg_p3p_ransac", "vgg_fmat_seven_point", "vgg_fmat_score",
             "vgg_fmat_eight_point", "vgg_fmat_residuals", "vgg_cholesky_solve_split", "vgg_ba_poll_done", "vgg_ba_tuning", "vgg_cholesky_solve_envelope", "vgg_ba_set_tile_rhs", "vgg_ba_set_step_from_factors", "vgg_triangulate_tracks_chunks_enqueue", "vgg_ba_set_tile_dma",
-            "vgg_sparse_depth", "vgg_depth_align_workspace_bytes", "vgg_depth_align", "vgg_depth_apply", "vgg_depth_unproject"]
+            "vgg_sparse_depth", "vgg_depth_align_workspace_bytes", "vgg_depth_align", "vgg_depth_apply", "vgg_depth_unproject",
+            "vgg_reproj_stats_workspace_bytes", "vgg_reproj_stats", "vgg_reproj_visible", "vgg_reproj_draw"]
 
 _lib = None
 
@@ -88,7 +89,8 @@ def lib():
         raise RuntimeError(f"libvggsfm_amd.so was built for {arch}, expected gfx950")
     for name in ("vgg_filter_points_workspace_bytes", "vgg_cam_from_img_workspace_bytes",
                  "vgg_triangulate_workspace_bytes", "vgg_triangulate_chunks_workspace_bytes", "vgg_ba_workspace_bytes",
-                 "vgg_cholesky_workspace_bytes", "vgg_p3p_ransac_workspace_bytes", "vgg_depth_align_workspace_bytes"):
+                 "vgg_cholesky_workspace_bytes", "vgg_p3p_ransac_workspace_bytes", "vgg_depth_align_workspace_bytes",
+                 "vgg_reproj_stats_workspace_bytes"):
         getattr(L, name).restype = ctypes.c_size_t
     L.vgg_ba_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     # a stale or variant build (VGGSFM_AMD_LIB) with another struct layout would be driven with shifted pointers: refuse it

@@ -232,3 +232,32 @@ class GeometryRunner:
         predictions["depth_dict"] = depth_dict
         predictions["unproj_dense_points3D"] = unproj
         return predictions
+
+    # ------------------------------------------------------------------ reprojection video (runner.py:834-885)
+    def make_reprojection_video(self, predictions, video_size, image_paths, original_images):
+        """runner.py:834-866: one padded BGR frame (numpy uint8) per image, in sorted-name order, with the visible sparse
+        observations drawn (vggsfm_amd.utils.utils.create_video_with_reprojections).  Reads the device-side
+        predictions["sparse_depth_device"] when extract_sparse_depth_and_point_from_reconstruction left it, so nothing of
+        the sparse depth goes through the host; otherwise predictions["sparse_depth"] / ["sparse_point"].
+        video_size: (width, height)."""
+        import os
+
+        from .utils.utils import create_video_with_reprojections
+
+        sparse_depth = predictions.get("sparse_depth_device")
+        if sparse_depth is None:
+            sparse_depth = predictions["sparse_depth"]
+        image_dir_prefix = os.path.dirname(image_paths[0])
+        image_paths = [os.path.basename(p) for p in image_paths]
+        return create_video_with_reprojections(image_dir_prefix, video_size, predictions["reconstruction"], image_paths,
+                                               sparse_depth, predictions.get("sparse_point"), original_images)
+
+    def save_reprojection_video(self, img_with_circles_list, video_size, output_dir):
+        """runner.py:868-885: writes output_dir/visuals/reproj.mp4 (needs OpenCV, see save_video_with_reprojections)."""
+        import os
+
+        from .utils.utils import save_video_with_reprojections
+
+        visual_dir = os.path.join(output_dir, "visuals")
+        os.makedirs(visual_dir, exist_ok=True)
+        save_video_with_reprojections(os.path.join(visual_dir, "reproj.mp4"), img_with_circles_list, video_size)

@@ -1,5 +1,7 @@
 """Camera-prediction averaging of the reference (vggsfm/utils/utils.py:25-187), as torch ops on the device, and its dense
-depth alignment (``align_dense_depth_maps``, utils.py:635-770) over the kernels of vggsfm_amd/dense_depth.py.
+depth alignment (``align_dense_depth_maps``, utils.py:635-770) over the kernels of vggsfm_amd/dense_depth.py, and its
+reprojection video (``filter_invisible_reprojections``, ``create_video_with_reprojections``, utils.py:393-546) over the
+kernels of vggsfm_amd/reproj_video.py.
 
 ``average_camera_prediction`` runs the (learned, injected) camera predictor several times, each time with a different
 frame swapped to position 0, brings every prediction back to the frame order and to the gauge of frame 0, and averages:
@@ -207,3 +209,70 @@ def align_dense_depth_maps(reconstruction, sparse_depth, disp_dict, original_ima
     if len(bad):
         DD.raise_for_status(status[bad[0]])
     return depth_dict, (cloud if visual_dense_point_cloud else None)
+
+
+def filter_invisible_reprojections(uvs_int, depths):
+    """utils.py:393-425 on the device (vggsfm_amd/reproj_video.py, csrc/reproj.hip): True for every point that wins its
+    integer pixel -- the smallest depth, ties to the lowest index, -0.0 == +0.0, a NaN depth first (np.argmin's rules).
+    numpy in -> numpy bool mask out; device tensors in -> device bool mask out.  The device grid covers the points'
+    bounding box: one of more than 2^27 pixels raises ValueError."""
+    from ..reproj_video import filter_mask
+
+    return filter_mask(uvs_int, depths)
+
+
+def create_video_with_reprojections(fname_prefix, video_size, reconstruction, image_paths, sparse_depth, sparse_point,
+                                    original_images=None, draw_radius=3, cmap="gist_rainbow", color_mode="dis_to_center",
+                                    *, device=None):
+    """utils.py:428-546 on the device (vggsfm_amd/reproj_video.py): one padded (H, W, 3) uint8 BGR numpy frame per name of
+    ``sorted(image_paths)`` with the visible observations drawn as filled circles of radius `draw_radius` in the colour of
+    their point (statistics, colours, centres, visibility and drawing order are the reference's exactly; the circles follow
+    the integer raster rule of DESIGN.md section 12, not OpenCV's anti-aliasing).
+
+    sparse_depth / sparse_point: the reference's dicts ({name: (n,3) [u, v, depth]} / {name: (n,4) [x, y, z, id]}), or
+    `sparse_depth` = the device-side :class:`vggsfm_amd.dense_depth.SparseDepth` (`sparse_point` is then not read).
+    original_images: {name: (h, w, 3) uint8 RGB} numpy arrays or device tensors; None reads ``fname_prefix/name`` with PIL
+    (its decoder, not OpenCV's).  An image without observations is output undrawn (the reference raises IndexError).
+    Raises NotImplementedError for an unknown `color_mode` and ValueError for a frame larger than `video_size` or a
+    negative `draw_radius`, before anything is launched."""
+    import os
+
+    from .. import dense_depth as DD
+    from .. import reproj_video as RV
+
+    dev = torch.device("cuda" if device is None else device)
+    names = sorted(image_paths)
+    if original_images is None:
+        from PIL import Image
+        images = {n: np.asarray(Image.open(os.path.join(fname_prefix, n)).convert("RGB")) for n in names}
+    else:
+        images = {n: original_images[n] for n in names}
+    RV._validate(images, video_size, draw_radius, color_mode)
+    if isinstance(sparse_depth, DD.SparseDepth):
+        sd = sparse_depth
+    else:
+        keys = list(sparse_depth)
+        uvd = [np.asarray(sparse_depth[k], np.float64).reshape(-1, 3) for k in keys]
+        xyzid = [np.asarray(sparse_point[k], np.float64).reshape(-1, 4) for k in keys]
+        obs_ptr = np.concatenate([[0], np.cumsum([len(u) for u in uvd])]).astype(np.int64)
+        cat = lambda a, c: torch.from_numpy(np.concatenate(a) if obs_ptr[-1] else np.zeros((0, c))).to(dev)
+        sd = DD.SparseDepth(keys, obs_ptr, cat(uvd, 3), cat(xyzid, 4))
+    xyz, ids = RV.live_points(reconstruction)
+    frames = RV.render(sd, xyz, ids, images, video_size, draw_radius=draw_radius, cmap=cmap, color_mode=color_mode,
+                       device=dev)
+    host = frames.cpu().numpy()
+    return [host[k] for k in range(len(names))]
+
+
+def save_video_with_reprojections(output_path, img_with_circles_list, video_size, fps=1):
+    """utils.py:549-571: the frames (BGR uint8, numpy or device tensors) as an mp4v video through OpenCV.  Encoding needs
+    OpenCV (``cv2``); without it this raises ImportError."""
+    try:
+        import cv2
+    except ImportError as e:
+        raise ImportError("save_video_with_reprojections needs OpenCV (the cv2 module) to encode the video; install "
+                          "opencv-python, or write the frames of create_video_with_reprojections yourself") from e
+    writer = cv2.VideoWriter(output_path, cv2.VideoWriter_fourcc(*"mp4v"), fps, tuple(int(v) for v in video_size))
+    for frame in img_with_circles_list:
+        writer.write(frame.cpu().numpy() if torch.is_tensor(frame) else np.asarray(frame))
+    writer.release()
