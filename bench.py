@@ -18,6 +18,13 @@ speed-up (`speedup_vs_n1`).  `--workload c4 --gpus N` makes the strong problem t
 Inputs are resident in HBM before the timed region; termination tests are disabled so that exactly K
 iterations run (a solve is restarted from the initial state every EPISODE iterations, like the
 reference's 50/100-iteration BA calls).
+
+A plain run does what the headline figure needs and nothing else: it sets the problem up, runs W warm-up and K timed
+iterations, writes --dump-outputs and prints the line.  Everything else the benchmark measures or checks runs only with
+`--full` (the `--no-*` options then leave out single legs): the second pass of the K steps under per-kernel HIP events
+(`ms_per_step_with_events`, `config.kernel_ms`, `roofline`, `roofline_by_kernel`), the strong- and weak-scaling legs and
+rank 0's solo run at N > 1, the CPU baseline and the GPU-vs-port comparisons, the triangulation, pipeline and configs[4]
+video legs.  The keys of legs that did not run are null.
 """
 import argparse
 import ctypes
@@ -330,6 +337,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c3 (BASELINE configs[2], one 100k-track shard per GPU) at every N")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run every other leg: the HIP-event pass (per-kernel times, roofline), "
+                         "scaling legs, CPU baseline, GPU-vs-port comparisons, triangulation, pipeline, configs[4] video; "
+                         "the --no-* options below select among them")
     ap.add_argument("--no-n1-leg", action="store_true", help="N > 1, strong scaling: skip rank 0's solo run of the whole problem")
     ap.add_argument("--no-parity-c4", action="store_true",
                     help="N = 1: skip the GPU-vs-port comparison of 3 LM iterations of the whole configs[3] problem (~1 min of CPU)")
@@ -361,6 +372,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    if not args.full:
+        # a plain run: the timed steps and the line, no other leg
+        args.no_n1_leg = args.no_weak_leg = args.no_strong_leg = args.no_cpu_baseline = True
+        args.no_parity_c4 = args.no_parity_c5 = args.no_triangulation = args.no_pipeline = True
     if args.overlap:
         BA.OVERLAP_FACTORIZATION = True
     if args.split_exchange:
@@ -505,12 +520,15 @@ def main():
     # The timed region runs UNOBSERVED; the per-kernel HIP events ride on a second pass of the same K steps right behind it.
     # An event pair around a launch costs ~5 us of stream time on each side on this stack (profiles/r05_timeline_c3.json: 54
     # of 1684 us per LM iteration of configs[2] were gaps next to the seven observed launches, none between the others), so
-    # observing inside the region made it 3 % slower than the work it times.  `ms_per_step_with_events` is the second pass.
+    # observing inside the region made it 3 % slower than the work it times.  `ms_per_step_with_events` is the second pass
+    # (--full only).
     dt, fin, _ = timed(prob, args.steps, args.warmup, False)
     if args.dump_outputs and rank == 0:
         # (before the profiled pass below, which goes on from this state)
         dump_outputs(caller_outputs(prob, *books[id(prob)], shared, cam_type, fin), args.dump_outputs)
-    dt_events, _, prof = timed(prob, args.steps, 0, True)
+    dt_events, prof = None, None
+    if args.full:
+        dt_events, _, prof = timed(prob, args.steps, 0, True)
     # ---- N > 1 with the strong problem as the main one: weak-scaling leg on configs[2] shards
     weak = None
     if world > 1 and strong_main and not args.no_weak_leg:
@@ -554,85 +572,87 @@ def main():
         n_red = int(fin["n_reduced"])
         bd = 6 if shared else 6 + (2 if cam_type == "SIMPLE_RADIAL" else 1)     # Schur block width
         y_slot = 12 if bd == 6 else 3 * bd                                         # doubles per observation in the segment buffer
-        # camera-pair blocks (a <= b) of the Schur complement, split by the launch that computes them
-        seg_count = torch.bincount(prob.obs_slot.long() // BA.GROUP, minlength=prob.num_segments).double()   # cameras per segment
-        pairs_all = float((counts * (counts + 1) / 2).sum().item())
-        pairs_diag = float((seg_count * (seg_count + 1) / 2).sum().item())       # both cameras in one 16-camera group
-        pairs_off = pairs_all - pairs_diag
-        if prob.merged_tile_launch:  # small problems: off-diagonal and diagonal tiles in one launch
-            pairs_off, pairs_diag = pairs_all, 0.0
-            ROCPROF_NAME["schur_tile<offdiag>"] = "schur_tile_merged_kernel"
-        # algorithmic work per launch (DESIGN.md "Kernels"): flops for the fp64-compute-bound kernels,
-        # bytes for the streaming kernels
-        work = {
-            "schur_tile<offdiag>": ("mfma", 2.0 * 3 * bd * bd * pairs_off),
-            "schur_tile<diag>": ("mfma", 2.0 * 3 * bd * bd * pairs_diag),
-            "cholesky": ("mfma", n_red ** 3 / 3.0 + 2.0 * n_red ** 2),
-            # (with the segment buffer it writes: 96 B per observation compressed, 24 BD B otherwise -- an artefact of the
-            #  formulation, priced because it is what bounds the kernel)
-            # (+ the 72-byte back-substitution block Z per point the diagonal tile launch reads when it forms the right-hand side)
-            "point_pass": ("hbm", (12.0 + 8.0 * y_slot) * n_obs + P * (24 + 4 + 8 * (6 + 3 + 6) + (72 if bd == 6 else 0))),
-            "point_step": ("hbm", 12.0 * n_obs + P * (24 + 4 + 8 * (6 + 3) + 24)),
-            "cam_pass<linearize>": ("hbm", 12.0 * n_obs + 24.0 * n_obs),
-            "cam_pass<rhs>": ("hbm", 12.0 * n_obs + (24.0 + 24 + 48) * n_obs),
-        }
-        # the roofline object describes the entry with the largest share of the timed region.  "cholesky" = the dataflow
-        # factorisation launch + the backward substitution (two launches per iteration; a latency-bound dependent chain,
-        # priced against the FP64 matrix peak like the tile kernels so that the fraction says how far it is from being
-        # a throughput problem)
-        # ("largest share" by kernel: the two launches of schur_tile_kernel -- off-diagonal and diagonal tiles -- count
-        #  together, and the object then describes the larger of the two launches.  Every entry's own fraction is in
-        #  `roofline_by_kernel`, so the line says the same thing whichever entry happens to lead on a given box.)
-        family = lambda k: "schur_tile" if k.startswith("schur_tile") else k
-        fam_ms = {}
-        for k, v in prof.items():
-            if v[1] == 0:
-                continue
-            fam_ms[family(k)] = fam_ms.get(family(k), 0.0) + v[0]
-        dom_family = max(fam_ms, key=fam_ms.get)
-        dom = max((k for k in prof if family(k) == dom_family), key=lambda k: prof[k][0])
-        by_kernel = {}
-        for k, (ms_k, launches_k) in prof.items():
-            if launches_k == 0:          # cam_pass<rhs> with 6 x 6 tile blocks: its sums come out of the diagonal tile launch
-                by_kernel[k] = dict(ms_per_iteration=0.0, bound=work[k][0], frac=None, launches=0)
-                continue
-            bound_k, amount_k = work[k]
-            per_iter_ms = ms_k / args.steps
-            rate = amount_k / max(per_iter_ms * 1e-3, 1e-12)          # work per iteration / time per iteration
-            peak = FP64_PEAK_TFLOPS * 1e12 if bound_k == "mfma" else HBM_PEAK_GBS * 1e9
-            by_kernel[k] = dict(ms_per_iteration=per_iter_ms, bound=bound_k, frac=rate / peak)
-        tot_ms, launches = prof[dom]
-        avg_ms = tot_ms / max(launches, 1)
-        bound, amount = work[dom]
-        per_iter = max(1, round(launches / args.steps))     # the tile kernels run once per batch
-        if dom == "cholesky":
-            per_iter = 1                                    # a group: time and work are per iteration
-            avg_ms = tot_ms / args.steps
-        amount = amount / per_iter
-        if bound == "mfma":
-            achieved = amount / (avg_ms * 1e-3) / 1e12
-            roof = dict(bound="mfma", achieved=achieved, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s",
-                        frac=achieved / FP64_PEAK_TFLOPS, traffic=None)
-        else:
-            achieved = amount / (avg_ms * 1e-3) / 1e9
-            roof = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
-                        traffic=None)
-        roof["traffic"], traffic_at = pmc_traffic(dom, args.workload)
-        roof.update(kernel=dom, avg_launch_ms=avg_ms, launches=launches, algorithmic_per_launch=amount,
-                    traffic_source="profiles/pmc_traffic_c3.json: (2 x FETCH_SIZE + WRITE_SIZE) KiB per launch, "
-                                   "rocprofv3 --pmc, separate passes; a committed summary, not a counter of this run"
-                                   if roof["traffic"] else None,
-                    traffic_measured_at=traffic_at,
-                    note="v_mfma_f64_16x16x4_f64 on the off-diagonal Schur tiles; algorithmic flops = 2*3*BD^2 per "
-                         "co-observing camera pair of a point (padding of the 16-camera segments not counted); "
-                         "FP64 MFMA peak = FP64 vector peak = 78.6 TFLOP/s"
-                         + (f"; --overlap: {per_iter} launches per iteration (tile batches), the first on all 256 CUs, the "
-                            f"others on {256 - BA.CHOL_CUS} CUs beside the factorisation, priced against the whole-chip peak"
-                            if per_iter > 1 else "") if dom.startswith("schur_tile") else "")
-        roof["launches_per_iteration"] = per_iter
-        # per ITERATION (tile kernels: sum over the batches; with overlap the entries are not additive -- the
-        # factorisation and the later tile batches run side by side)
-        kernel_ms = {k: (v[0] / args.steps) for k, v in prof.items()}
+        roof = by_kernel = kernel_ms = None
+        if prof is not None:          # (--full: the HIP-event pass ran)
+            # camera-pair blocks (a <= b) of the Schur complement, split by the launch that computes them
+            seg_count = torch.bincount(prob.obs_slot.long() // BA.GROUP, minlength=prob.num_segments).double()   # cameras per segment
+            pairs_all = float((counts * (counts + 1) / 2).sum().item())
+            pairs_diag = float((seg_count * (seg_count + 1) / 2).sum().item())       # both cameras in one 16-camera group
+            pairs_off = pairs_all - pairs_diag
+            if prob.merged_tile_launch:  # small problems: off-diagonal and diagonal tiles in one launch
+                pairs_off, pairs_diag = pairs_all, 0.0
+                ROCPROF_NAME["schur_tile<offdiag>"] = "schur_tile_merged_kernel"
+            # algorithmic work per launch (DESIGN.md "Kernels"): flops for the fp64-compute-bound kernels,
+            # bytes for the streaming kernels
+            work = {
+                "schur_tile<offdiag>": ("mfma", 2.0 * 3 * bd * bd * pairs_off),
+                "schur_tile<diag>": ("mfma", 2.0 * 3 * bd * bd * pairs_diag),
+                "cholesky": ("mfma", n_red ** 3 / 3.0 + 2.0 * n_red ** 2),
+                # (with the segment buffer it writes: 96 B per observation compressed, 24 BD B otherwise -- an artefact of the
+                #  formulation, priced because it is what bounds the kernel)
+                # (+ the 72-byte back-substitution block Z per point the diagonal tile launch reads when it forms the right-hand side)
+                "point_pass": ("hbm", (12.0 + 8.0 * y_slot) * n_obs + P * (24 + 4 + 8 * (6 + 3 + 6) + (72 if bd == 6 else 0))),
+                "point_step": ("hbm", 12.0 * n_obs + P * (24 + 4 + 8 * (6 + 3) + 24)),
+                "cam_pass<linearize>": ("hbm", 12.0 * n_obs + 24.0 * n_obs),
+                "cam_pass<rhs>": ("hbm", 12.0 * n_obs + (24.0 + 24 + 48) * n_obs),
+            }
+            # the roofline object describes the entry with the largest share of the timed region.  "cholesky" = the dataflow
+            # factorisation launch + the backward substitution (two launches per iteration; a latency-bound dependent chain,
+            # priced against the FP64 matrix peak like the tile kernels so that the fraction says how far it is from being
+            # a throughput problem)
+            # ("largest share" by kernel: the two launches of schur_tile_kernel -- off-diagonal and diagonal tiles -- count
+            #  together, and the object then describes the larger of the two launches.  Every entry's own fraction is in
+            #  `roofline_by_kernel`, so the line says the same thing whichever entry happens to lead on a given box.)
+            family = lambda k: "schur_tile" if k.startswith("schur_tile") else k
+            fam_ms = {}
+            for k, v in prof.items():
+                if v[1] == 0:
+                    continue
+                fam_ms[family(k)] = fam_ms.get(family(k), 0.0) + v[0]
+            dom_family = max(fam_ms, key=fam_ms.get)
+            dom = max((k for k in prof if family(k) == dom_family), key=lambda k: prof[k][0])
+            by_kernel = {}
+            for k, (ms_k, launches_k) in prof.items():
+                if launches_k == 0:          # cam_pass<rhs> with 6 x 6 tile blocks: its sums come out of the diagonal tile launch
+                    by_kernel[k] = dict(ms_per_iteration=0.0, bound=work[k][0], frac=None, launches=0)
+                    continue
+                bound_k, amount_k = work[k]
+                per_iter_ms = ms_k / args.steps
+                rate = amount_k / max(per_iter_ms * 1e-3, 1e-12)          # work per iteration / time per iteration
+                peak = FP64_PEAK_TFLOPS * 1e12 if bound_k == "mfma" else HBM_PEAK_GBS * 1e9
+                by_kernel[k] = dict(ms_per_iteration=per_iter_ms, bound=bound_k, frac=rate / peak)
+            tot_ms, launches = prof[dom]
+            avg_ms = tot_ms / max(launches, 1)
+            bound, amount = work[dom]
+            per_iter = max(1, round(launches / args.steps))     # the tile kernels run once per batch
+            if dom == "cholesky":
+                per_iter = 1                                    # a group: time and work are per iteration
+                avg_ms = tot_ms / args.steps
+            amount = amount / per_iter
+            if bound == "mfma":
+                achieved = amount / (avg_ms * 1e-3) / 1e12
+                roof = dict(bound="mfma", achieved=achieved, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s",
+                            frac=achieved / FP64_PEAK_TFLOPS, traffic=None)
+            else:
+                achieved = amount / (avg_ms * 1e-3) / 1e9
+                roof = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
+                            traffic=None)
+            roof["traffic"], traffic_at = pmc_traffic(dom, args.workload)
+            roof.update(kernel=dom, avg_launch_ms=avg_ms, launches=launches, algorithmic_per_launch=amount,
+                        traffic_source="profiles/pmc_traffic_c3.json: (2 x FETCH_SIZE + WRITE_SIZE) KiB per launch, "
+                                       "rocprofv3 --pmc, separate passes; a committed summary, not a counter of this run"
+                                       if roof["traffic"] else None,
+                        traffic_measured_at=traffic_at,
+                        note="v_mfma_f64_16x16x4_f64 on the off-diagonal Schur tiles; algorithmic flops = 2*3*BD^2 per "
+                             "co-observing camera pair of a point (padding of the 16-camera segments not counted); "
+                             "FP64 MFMA peak = FP64 vector peak = 78.6 TFLOP/s"
+                             + (f"; --overlap: {per_iter} launches per iteration (tile batches), the first on all 256 CUs, the "
+                                f"others on {256 - BA.CHOL_CUS} CUs beside the factorisation, priced against the whole-chip peak"
+                                if per_iter > 1 else "") if dom.startswith("schur_tile") else "")
+            roof["launches_per_iteration"] = per_iter
+            # per ITERATION (tile kernels: sum over the batches; with overlap the entries are not additive -- the
+            # factorisation and the later tile batches run side by side)
+            kernel_ms = {k: (v[0] / args.steps) for k, v in prof.items()}
         # whole-iteration view of SURVEY.md section 8(d): algorithmic bytes / flops of one LM iteration
         t_iter = dt / args.steps
         k_intr = n_red - 6 * S
@@ -823,7 +843,7 @@ def main():
             "lm_iterations_per_s_global": args.steps / dt,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps,
-            "ms_per_step_with_events": 1e3 * dt_events / args.steps,
+            "ms_per_step_with_events": None if dt_events is None else 1e3 * dt_events / args.steps,
             "higher_is_better": True, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": (f"synthetic {S} frames x {N} tracks split over {world} rank(s), {cam_type} per-frame intrinsics, "

@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$1; shift
 ROUNDS=${ROUNDS:-2}
-ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --no-cpu-baseline --no-strong-leg --no-triangulation --no-pipeline}
+ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5 --no-cpu-baseline --no-strong-leg --no-triangulation --no-pipeline}
 : > $OUT
 cd $ROOT
 for r in $(seq 1 $ROUNDS); do

@@ -4,7 +4,7 @@
 # ba.compile_problem) against HEAD, interleaved.
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd $ROOT
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-strong-leg --no-triangulation --no-pipeline"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-strong-leg --no-triangulation --no-pipeline"
 emit() { python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print(json.dumps(dict(variant='$1', round=$2, ms_per_step=d['ms_per_step'], ms_per_step_with_events=d['ms_per_step_with_events'], value=d['value'], kernel_ms=d['config']['kernel_ms'])))"; }

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/tile_diag
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L 2>/dev/null | grep -o "SQ_[A-Z0-9_]*" | sort -u > $OUT/sq_counter_names.txt
-BENCH="python bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-strong-leg --no-triangulation --no-pipeline"
+BENCH="python bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-strong-leg --no-triangulation --no-pipeline"
 pass() {   # name, counters
   rm -rf /tmp/pmc_$1
   (cd $ROOT && timeout 300 rocprofv3 --kernel-trace --pmc $2 --output-format csv -d /tmp/pmc_$1 -- $BENCH > $OUT/pass_$1.log 2>&1)

@@ -1,7 +1,7 @@
 """the driver's multi-GPU command line, rehearsed end to end before its first real run.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus 2 --steps K --warmup W
+        bench.py --gpus 2 --steps K --warmup W [--full]
 
 Only one GPU is visible on the test box, so the two ranks SHARE it and the collectives go over gloo, staged through the host
 (``VGGSFM_BENCH_BACKEND=gloo`` -- bench.py's rehearsal switch; the measured path is RCCL).  Everything else is the code the
@@ -12,7 +12,8 @@ strong-scaling leg on it, the ONE JSON line on rank 0.
 
 Round 5: `value` means the same thing at every N -- configs[2] shard-iterations per second, one
 100k-track shard per GPU -- so value(N) / value(1) is a scaling curve; the strong-scaling figure on configs[3] rides along as
-the key `strong_scaling_c4` with its own N = 1 point.  Asserted here for the N = 2 line against the N = 1 line's fields."""
+the key `strong_scaling_c4` with its own N = 1 point.  Asserted here for the N = 2 line against the N = 1 line's fields, with
+`--full` (a plain run times the main problem alone; the scaling legs and the roofline are part of the full run)."""
 import json
 import os
 import socket
@@ -38,7 +39,7 @@ def test_bench_two_ranks_command_line_over_gloo():
     env = dict(os.environ, VGGSFM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--strong-steps", "3"]
+           "--strong-steps", "3", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
