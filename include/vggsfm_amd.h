@@ -230,7 +230,8 @@ int vgg_ba_solve(const vgg_ba_problem* problem, const vgg_ba_options* options, v
  *   phase 3 UPDATE   : trust-region decision, commit
  *   phase 4 / 5      : pack / unpack the lower triangle of the reduced system + rhs into / from reduce buffer 4
  *                      (n(n+1)/2 + n doubles): all-reducing buffer 4 between them replaces the all-reduce of
- *                      buffer 1 (n^2 + n doubles, upper triangle all zero) at half the payload
+ *                      buffer 1 (n^2 + n doubles, strict upper triangle all zero: vgg_ba_begin clears it, no phase writes
+ *                      it) at half the payload
  *   phase 6          : unpack from the OUTPUT of a reduce-scatter + all-gather of buffer 4, read in place: with W ranks
  *                      and c = ceil(count / W), phase 4 also zeroes buffer 4 up to W c doubles (it is carved with that
  *                      padding: the reduce-scatter input, no staging copy) and puts the rank's gradient maximum at
@@ -248,7 +249,8 @@ int vgg_ba_solve(const vgg_ba_problem* problem, const vgg_ba_options* options, v
  *                      workspace --, VGG_ERR_UNSUPPORTED otherwise (nothing is launched).  With a = vgg_ba_reduce_buffer(7) elements in
  *                      part A, b = count(4) - a, ca = ceil(a / W), cb = ceil(b / W): buffer 4 = [A: W ca | B: W cb] (reduce-
  *                      scatter inputs), buffer 5 = [A: ca | B: cb + 1] (the rank's slices; the gradient maximum rides behind
- *                      B's), buffer 6 = [A: W ca | B: W (cb + 1)] (all-gather outputs)
+ *                      B's), buffer 6 = [A: W ca | B: W (cb + 1)] (all-gather outputs); buffers 4 and 6 are carved with the
+ *                      padding both forms need up to W = 1024 (count(6) = count(4) + 3072)
  * vgg_ba_reduce_buffer returns the device address / element count (doubles) of each reduce buffer (which = 7: buffer 4's address
  * and the element count of part A). */
 int vgg_ba_begin(const vgg_ba_problem* problem, const vgg_ba_options* options, void* workspace, size_t workspace_bytes,

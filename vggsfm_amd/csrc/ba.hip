@@ -129,7 +129,7 @@ struct Ws {  // device workspace carve-up (pointers into the caller's buffer)
   double* T;                  // [C][BDp][1+kdsh]
   double* part_B;             // [kMaxWG] per-workgroup gradient max
   double* part_F;             // [kMaxWG][4]
-  double* packed;             // lower triangle of S (row by row) + rhs: the multi-GPU reduce payload, followed by kPackPad
+  double* packed;             // lower triangle of S (row by row) + rhs: the multi-GPU reduce payload, followed by 2 kPackPad
   size_t packed_count;        //   doubles of padding (the reduce-scatter input is W equal slices: W ceil(count / W) doubles)
   double* pk_mine;            // [ceil(count / W) + 1] this rank's reduced slice + its local gradient maximum (reduce-scatter
                               //   output = all-gather input)
@@ -200,9 +200,11 @@ static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, 
   w.S = w.sys; w.rhs = w.S + (size_t)d.n_red * d.n_red;
   w.S2 = (double*)take(8ull * (size_t)d.n_red * d.n_red);
   w.packed_count = (size_t)d.n_red * (d.n_red + 1) / 2 + d.n_red;
-  w.packed = (double*)take(8ull * (w.packed_count + kPackPad));
+  // padding for W <= kPackPad ranks: the one-piece exchange needs W c <= count + W - 1 in `packed` and W (c + 1) <= count + 2W - 1
+  // in `pk_gathered`; the split exchange rounds two parts up, W (ca + cb) <= count + 2 (W - 1) and W ca + W (cb + 1) <= count + 3W - 2
+  w.packed = (double*)take(8ull * (w.packed_count + 2 * kPackPad));
   w.pk_mine = (double*)take(8ull * (w.packed_count + 2));                      // (W = 1: the whole payload)
-  w.pk_gathered = (double*)take(8ull * (w.packed_count + 2 * kPackPad));
+  w.pk_gathered = (double*)take(8ull * (w.packed_count + 3 * kPackPad));
   w.gmax_pts = (double*)take(64);
   w.stepsum = (double*)take(64);
   w.G = (double*)take(8ull * 6 * d.P); w.hs = (double*)take(8ull * 3 * d.P);
@@ -392,8 +394,9 @@ __global__ void init_kernel(DevProblem pb, Ws w, vgg_ba_options opt, int rank, i
 // Zeroes the part of the reduced system S | rhs that anything reads: only the lower triangle is ever filled (tile_reduce_kernel
 // and assemble_kernel write S[hi][lo], the factorisation and pack_lower_kernel read it), so row i is cleared up to the end of
 // the 64-column block of its diagonal element and the upper triangle is left alone -- half the stores of a full clear (at the
-// 6002 x 6002 system of the final joint adjustment of configs[4]: 144 of 288 MB per iteration).  Workgroup `wg` of `nwg` takes
-// the rows wg, wg + nwg, ...; row n is the right-hand side.
+// 6002 x 6002 system of the final joint adjustment of configs[4]: 144 of 288 MB per iteration; vgg_ba_begin clears the whole
+// S | rhs once, so with the phase API the upper triangle stays zero).  Workgroup `wg` of `nwg` takes the rows wg, wg + nwg, ...;
+// row n is the right-hand side.
 __device__ __forceinline__ void zero_system_lower(const Ws& w, int n, int wg, int nwg) {
   const bool even = (n & 1) == 0;                 // (rows 16-byte aligned)
   for (int row = wg; row <= n; row += nwg) {
@@ -3213,6 +3216,9 @@ int vgg_ba_begin(const vgg_ba_problem* problem, const vgg_ba_options* options, v
   if (workspace_bytes < L.w.total_bytes) return VGG_ERR_WORKSPACE;
   if (world_size < 1 || world_size > kPackPad || rank < 0 || rank >= world_size) return VGG_ERR_INVALID_ARGUMENT;
   VGG_HIP_CHECK(hipMemsetAsync(L.w.Y, 0, L.w.y_bytes, L.st));   // absent slots stay zero for the whole solve
+  // the whole S | rhs once: the phases clear and fill only the lower triangle (zero_system_lower), and nothing writes the
+  // strict upper one, so it stays zero -- reduce buffer 1 as include/vggsfm_amd.h describes it
+  VGG_HIP_CHECK(hipMemsetAsync(L.w.sys, 0, sizeof(double) * L.w.sys_count, L.st));
   init_kernel<<<div_up(L.d.n_red > 0 ? L.d.n_red : 1, 256), 256, 0, L.st>>>(L.dp, L.w, L.opt, rank, world_size);
   VGG_LAUNCH_CHECK();
   return VGG_OK;
@@ -3240,7 +3246,7 @@ int vgg_ba_reduce_buffer(const vgg_ba_problem* problem, const vgg_ba_options* op
     case 3: *device_ptr = w.stepsum; *count = 4; break;
     case 4: *device_ptr = w.packed; *count = w.packed_count; break;
     case 5: *device_ptr = w.pk_mine; *count = w.packed_count + 2; break;
-    case 6: *device_ptr = w.pk_gathered; *count = w.packed_count + 2 * kPackPad; break;
+    case 6: *device_ptr = w.pk_gathered; *count = w.packed_count + 3 * kPackPad; break;
     case 7: *device_ptr = w.packed; *count = split_count_a(d); break;      // (count = elements of part A of the split exchange)
     default: return VGG_ERR_INVALID_ARGUMENT;
   }

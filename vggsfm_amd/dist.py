@@ -290,6 +290,7 @@ class ShardedBA:
         M = self.bufs[4].numel()
         chunk = -(-M // max(world_size, 1))
         off4 = self.bufs[4].data_ptr() - self.ws.data_ptr()
+        assert world_size * (chunk + 1) <= self.bufs[6].numel(), "one-piece exchange: buffer 6 too small for world_size"
         self._padded = self.ws[off4:off4 + 8 * world_size * chunk].view(torch.float64)
         self._mine = self.bufs[5][:chunk + 1]
         self._gathered = self.bufs[6][:world_size * (chunk + 1)]
@@ -307,6 +308,10 @@ class ShardedBA:
                 W = max(world_size, 1)
                 a = int(cnt.value)
                 ca, cb = -(-a // W), -(-(M - a) // W)
+                off5 = self.bufs[5].data_ptr() - self.ws.data_ptr()
+                # the split regions must fit the carve: buffer 4's up to buffer 5, buffer 6's within its count
+                assert off4 + 8 * W * (ca + cb) <= off5, "split exchange: buffer 4 region overruns buffer 5"
+                assert W * ca + W * (cb + 1) <= self.bufs[6].numel(), "split exchange: buffer 6 region overruns its carve"
                 b4 = self.ws[off4:off4 + 8 * W * (ca + cb)].view(torch.float64)
                 self._padded_a, self._padded_b = b4[:W * ca], b4[W * ca:]
                 self._mine_a, self._mine_b = self.bufs[5][:ca], self.bufs[5][ca:ca + cb + 1]
