@@ -222,12 +222,17 @@ int vgg_ba_solve(const vgg_ba_problem* problem, const vgg_ba_options* options, v
 
 /* Multi-GPU (points sharded across ranks, cameras replicated): the same loop split into phases so
  * that the host can interleave RCCL all-reduces on the same stream.
- *   vgg_ba_begin    : init control block
- *   phase 0 LINEARIZE: camera-side J^T J / J^T r / cost of the local points  -> reduce buffer 0 (SUM)
+ *   vgg_ba_begin    : init control block; camera-side J^T J / J^T r / cost of the local points at the start point
+ *                      -> reduce buffer 0
+ *   phase 0 LINEARIZE: launches nothing: reduce buffer 0 holds the local camera-side terms of the current x    -> SUM
  *   phase 1 SCHUR    : point blocks, reduced camera system of the local points -> reduce buffer 1 (SUM),
  *                      gradient max of local points                            -> reduce buffer 2 (MAX)
- *   phase 2 STEP     : Cholesky + back-substitution + candidate cost         -> reduce buffer 3 (SUM)
- *   phase 3 UPDATE   : trust-region decision, commit
+ *   phase 2 STEP     : Cholesky + back-substitution, then the camera-side pass at the candidate: its local cost, the
+ *                      model cost change and the step norms                    -> reduce buffer 3 (SUM); its local
+ *                      J^T J / J^T r / cost are kept in the workspace (not a reduce buffer)
+ *   phase 3 UPDATE   : trust-region decision, commit.  Accepted: the candidate's local terms of phase 2 are copied into
+ *                      reduce buffer 0 (the next phase 0 needs no pass).  Rejected: buffer 0 keeps the all-reduced terms of
+ *                      the current x on rank 0 and is cleared on the other ranks, so that the next SUM gives them back
  *   phase 4 / 5      : pack / unpack the lower triangle of the reduced system + rhs into / from reduce buffer 4
  *                      (n(n+1)/2 + n doubles): all-reducing buffer 4 between them replaces the all-reduce of
  *                      buffer 1 (n^2 + n doubles, strict upper triangle all zero: vgg_ba_begin clears it, no phase writes

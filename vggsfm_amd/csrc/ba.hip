@@ -14,7 +14,7 @@
 //                         camera-major CSR (col_ptr, cobs_pt i32, cobs_uv f32x2)
 //   reduced camera system S[n,n] (lower, row-major), n = 6C + kd*NI
 // Kernels per LM iteration (algorithmic bytes in DESIGN.md):
-//   cam_pass<LIN>   camera-major: U_c = F^T F, g_c = F^T r, cost            (only after an accepted step)
+//   cam_pass<LIN>   camera-major: U_c = F^T F, g_c = F^T r, cost            (vgg_ba_begin only: at the start point)
 //   point_pass      point-major, one wavefront per point: V_p = E^T E + D^2, its Cholesky inverse,
 //                   h_p = V^-1 E^T r, shared-intrinsics coupling
 //   cam_pass<RHS>   camera-major: F^T (r - E h_p) and the shared-intrinsics Schur terms
@@ -22,7 +22,9 @@
 //                   block of cameras (I*16+a, J*16+b) in registers, Y blocks staged through LDS
 //   assemble        diagonal blocks, damping, constant columns
 //   cholesky        chol.hip (matrix-core trailing update)
-//   point_step      back-substitution, model cost change, candidate cost
+//   point_step      back-substitution, model cost change, candidate points
+//   cam_pass<CAND>  the same camera-major pass at the candidate: its cost decides the step, and on acceptance its U_c, g_c
+//                   are the next linearisation (no pass at the start of the next iteration)
 //   control         Ceres' accept / reject logic, one workgroup
 #include <type_traits>
 
@@ -153,6 +155,10 @@ struct Ws {  // device workspace carve-up (pointers into the caller's buffer)
   double* Yx;                 // [num_segments + 1][3][96]: a segment as the tile kernels hold it in LDS (component-major rows)
   size_t yx_bytes;
   int tile_dma;
+  // the linearisation at the candidate (cam_pass<CAND>, same layout as `lin`): carved behind everything else so that no
+  // other buffer moves; commit_kernel copies it into `lin` when the step is accepted
+  double* lin_cand;
+  double *U_cand, *g_cand, *cost_cand;
   size_t lin_count, sys_count, total_bytes;
 };
 
@@ -232,6 +238,8 @@ static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, 
   w.part_Q = (double*)take(8ull * kMaxWG * 8);
   w.rz = (double*)take(8ull * (size_t)((d.C + kGroup - 1) / kGroup) * kGroup * 6 * 3);
   w.split_off = (unsigned long long*)take(8ull * 2 * ((size_t)d.n_red + 2));
+  w.lin_cand = (double*)take(8ull * w.lin_count);
+  w.U_cand = w.lin_cand; w.g_cand = w.U_cand + (size_t)d.C * d.BDp * d.BDp; w.cost_cand = w.g_cand + (size_t)d.C * d.BDp;
   w.tile_rhs = 0;
   w.total_bytes = off;
   return w;
@@ -412,7 +420,8 @@ __device__ __forceinline__ void zero_system_lower(const Ws& w, int n, int wg, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// camera-major pass.  MODE 0: linearisation terms U_c, g_c, cost.  MODE 1: T_c = F^T [r - E hs | -E Ms].
+// camera-major pass.  MODE 0: linearisation terms U_c, g_c, cost at (pb.cam_q, pb.cam_t, pb.intr, pb.pts) into w.U, w.g,
+// w.costc -- the start point (vgg_ba_begin) or the candidate (phase 2, launch_linearize).  MODE 1: T_c = F^T [r - E hs | -E Ms].
 template <int KD, int MODE>
 __global__ __launch_bounds__(256, (MODE == 1) ? VGG_CP_OCC_RHS : VGG_CP_OCC) void cam_pass_kernel(DevProblem pb, Ws w) {
   constexpr int BD = 6 + KD;
@@ -421,7 +430,6 @@ __global__ __launch_bounds__(256, (MODE == 1) ? VGG_CP_OCC_RHS : VGG_CP_OCC) voi
   __shared__ double red[4 * NV];
   __shared__ double tot[NV];
   if (w.ctl->done) return;
-  if (MODE == 0 && !w.ctl->need_lin) return;
   if (MODE == 1) {
     // Zero the reduced system S | rhs for the tile sums and assemble_kernel that follow (nothing touches it in between, and
     // the previous iteration is done with it): a few 16-byte stores per thread here instead of a fill launch
@@ -534,7 +542,6 @@ __global__ __launch_bounds__(64) void cam_reduce_kernel(DevProblem pb, Ws w, int
   constexpr int NU = BD * (BD + 1) / 2;
   constexpr int NV = (MODE == 0) ? (NU + BD + 1) : (BD * (1 + KD));
   if (w.ctl->done) return;
-  if (MODE == 0 && !w.ctl->need_lin) return;
   if (MODE == 1 && blockIdx.x == 0) {            // (rides along: max of the point passes' per-workgroup gradient norms)
     double m = 0;
     for (int i = threadIdx.x; i < point_parts; i += 64) m = fmax(m, w.part_B[i]);
@@ -2323,15 +2330,18 @@ __global__ void cam_update_kernel(DevProblem pb, Ws w) {
   w.cam_part[3 * c + 2] = mc;
 }
 
-// back-substitution, model cost change, candidate point and candidate cost: LPP lanes per point (see point_pass_kernel)
+// back-substitution, model cost change and candidate point: LPP lanes per point (see point_pass_kernel).  The candidate's
+// cost is not evaluated here: cam_pass<CAND> behind this launch evaluates the candidate's residuals with their Jacobians, and
+// its cost decides the step.  (A second sweep here used to evaluate the same residuals for the cost alone, and after an
+// accepted step cam_pass<LIN> evaluated them once more; c3: this launch 0.101 -> 0.079 ms without that sweep.)
 // FYM = 1 (round 4, OPT-IN: vgg_ba_set_step_from_factors / VGG_STEP_FACTORS; measured SLOWER, see below): the tile blocks
 // are 6 x 6 and the segment buffer holds the compressed Schur factors N = Jw^T (E G), 2 a of every observation
 // (point_pass_kernel, CY).  Then E^T F dy -- all this kernel needs of the Jacobians -- is there already:
 // F_pose dy = Jw (dy_t - 2 a x dy_w), so G^T sum E^T F dy = sum N^T (dy_t - 2 a x dy_w): one 96-byte record and ~25
 // multiply-adds per observation instead of a second evaluation of the projection and its Jacobians (~150 FP64 operations);
 // the shared intrinsics' share is Ms (dy_a / scale) per point, and the part of the model cost change that only depends on
-// the camera step comes from the cameras' U, g (cam_update_kernel).  The candidate's residuals are still evaluated here.
-// Same step to rounding (tests/test_gpu_ba.py::test_ba_step_from_factors_matches_evaluation).  c3, same box
+// the camera step comes from the cameras' U, g (cam_update_kernel).  Same step to rounding
+// (tests/test_gpu_ba.py::test_ba_step_from_factors_matches_evaluation).  c3, same box
 // (profiles/r04_ab_step_from_factors_c3.jsonl): 0.143 ms re-evaluating (210 VGPRs, 2 wavefronts / SIMD, FP64 issue bound),
 // 0.170 ms from the factors (160 VGPRs, 3 wavefronts / SIMD): a point's records lie in as many segments as it has
 // observations, each 96-byte record touches 1.5 cache lines on average -- 5 M x 192 B = 0.96 GB of line traffic in 0.17 ms
@@ -2342,31 +2352,28 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
   constexpr bool FY = FYM == 1;                  // every observation from its factor
   constexpr bool HY = FYM == 2;                  // (measurement only) odd sweeps from the factors, even sweeps re-evaluated
   constexpr int BD = 6 + KD;
-  __shared__ double red[4][4];
-  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy_pose[6C] cand R[9C] cand_t[3C] flags[C]   (FY: dy, cand R, cand t only)
+  __shared__ double red[4][3];
+  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy_pose[6C] flags[C]   (FY: dy only)
   if (w.ctl->done) return;
   const Dims& d = pb.d;
   constexpr int PPW = 64 / LPP;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sub = lane / LPP, sl = lane % LPP;
   const int nw = gridDim.x * 4 * PPW;
-  double s_cost = 0, s_mcc = 0, s_step = 0, s_xn = 0;
+  double s_mcc = 0, s_step = 0, s_xn = 0;
   const double* lq = cam_cache;                  // rotation matrices [9C]
   const double* lt = lq + (FY ? 0 : 9 * d.C);
   const double* ldy = lt + (FY ? 0 : 3 * d.C);
-  const double* lcq = ldy + 6 * d.C;             // rotation matrices of the candidate [9C]
-  const double* lct = lcq + 9 * d.C;
-  const double* lfl = lct + 3 * d.C;
+  const double* lfl = ldy + 6 * d.C;
   if (LDSCAM) {
     double* cc = cam_cache;
-    for (int i = threadIdx.x; i < d.C; i += 256) {
-      if (!FY) {
+    if (!FY) {
+      for (int i = threadIdx.x; i < d.C; i += 256) {
         quat_to_R(pb.cam_q + 4 * i, cc + 9 * i);
-        cc[30 * d.C + i] = pb.cam_const ? (double)pb.cam_const[i] : 0.0;
+        cc[18 * d.C + i] = pb.cam_const ? (double)pb.cam_const[i] : 0.0;
       }
-      quat_to_R(w.cand_q + 4 * i, cc + (lcq - cam_cache) + 9 * i);
+      for (int i = threadIdx.x; i < 3 * d.C; i += 256) cc[9 * d.C + i] = pb.cam_t[i];
     }
-    for (int i = threadIdx.x; i < 3 * d.C; i += 256) { if (!FY) cc[9 * d.C + i] = pb.cam_t[i]; cc[(lct - cam_cache) + i] = w.cand_t[i]; }
     for (int i = threadIdx.x; i < 6 * d.C; i += 256) cc[(ldy - cam_cache) + i] = w.dy[i];
     __syncthreads();
   }
@@ -2425,7 +2432,7 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
     //   sum [F dy . r - |F dy|^2 / 2]  +  ys^T g - ys^T t3 - ys^T V ys / 2        (g = sum E^T r, t3 = sum E^T F dy, V = sum E^T E)
     // and with (V + D^2) ys = g - t3 and (V + D^2)^-1 = G G^T (point_pass):  ys^T (g - t3) = |G^-1 ys|^2 =: |z|^2, so
     //   = sum [F dy . r - |F dy|^2 / 2]  +  |z|^2 / 2  +  ys^T D^2 ys / 2.
-    // The bracket is accumulated in the first sweep; the second sweep only evaluates the candidate's residuals.
+    // The bracket is accumulated in the sweep.
     double uf[3] = {0, 0, 0};                      // G^T sum E^T F_pose dy over the observations taken from their factors
     auto from_factor = [&](int pass, int o) __attribute__((always_inline)) {
       const int c = f_pf.cam(pass, pb.obs_cam, o);
@@ -2486,9 +2493,8 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
         ys[0] -= Msp[3 * m] * ds; ys[1] -= Msp[3 * m + 1] * ds; ys[2] -= Msp[3 * m + 2] * ds;
       }
     }
-    const double Xn[3] = {X[0] - ys[0], X[1] - ys[1], X[2] - ys[2]};
     if (sl == 0) {
-      w.cand_pts[3 * (size_t)p] = Xn[0]; w.cand_pts[3 * (size_t)p + 1] = Xn[1]; w.cand_pts[3 * (size_t)p + 2] = Xn[2];
+      w.cand_pts[3 * (size_t)p] = X[0] - ys[0]; w.cand_pts[3 * (size_t)p + 1] = X[1] - ys[1]; w.cand_pts[3 * (size_t)p + 2] = X[2] - ys[2];
       s_step += ys[0] * ys[0] + ys[1] * ys[1] + ys[2] * ys[2];
       if (!pt_c) s_xn += X[0] * X[0] + X[1] * X[1] + X[2] * X[2];
       if (G22 != 0.0) {                                  // (constant / unobserved points: G = 0, ys = 0)
@@ -2496,31 +2502,21 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
         s_mcc += 0.5 * (z0 * z0 + z1 * z1 + z2 * z2) + 0.5 * (pd0 * ys[0] * ys[0] + pd1 * ys[1] * ys[1] + pd2 * ys[2] * ys[2]);
       }
     }
-    // candidate residuals.  (Measured and rejected, round 4: two observations of a lane evaluated side by side so that
-    //  their dependent fp64 chains interleave -- 0.143 -> 0.150 ms at configs[2]; the sweep is not bound by its chain.)
-    for (int o = o0 + sl; o < o1; o += LPP) {
-      const int pass = (o - o0) / LPP;
-      const int c = f_pf.cam(pass, pb.obs_cam, o);
-      const int a = d.shared ? 0 : c;
-      const float2 uv = f_pf.uv(pass, pb.obs_uv, o);
-      double rc[2];
-      if (LDSCAM) obs_residual_R(d.model, lcq + 9 * c, lct + 3 * c, w.cand_intr + 4 * a, Xn, (double)uv.x, (double)uv.y, rc);
-      else obs_residual_R(d.model, CamR(w.cand_q + 4 * c).R, w.cand_t + 3 * c, w.cand_intr + 4 * a, Xn, (double)uv.x, (double)uv.y, rc);
-      s_cost += loss_rho0(d, rc[0] * rc[0] + rc[1] * rc[1]);
-    }
   }
-  s_cost = wave_sum(s_cost); s_mcc = wave_sum(s_mcc); s_step = wave_sum(s_step); s_xn = wave_sum(s_xn);
-  if (lane == 0) { red[wave][0] = s_cost; red[wave][1] = s_mcc; red[wave][2] = s_step; red[wave][3] = s_xn; }
+  s_mcc = wave_sum(s_mcc); s_step = wave_sum(s_step); s_xn = wave_sum(s_xn);
+  if (lane == 0) { red[wave][0] = s_mcc; red[wave][1] = s_step; red[wave][2] = s_xn; }
   __syncthreads();
-  if (threadIdx.x < 4) w.part_F[4 * blockIdx.x + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  if (threadIdx.x < 3) w.part_F[4 * blockIdx.x + 1 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-__global__ __launch_bounds__(256) void reduce_step_kernel(Ws w, int nparts) {
+// reduce buffer 3: [0] the candidate's cost (sum over the cameras of cam_pass<CAND>'s sums), [1..3] the point_step sums
+__global__ __launch_bounds__(256) void reduce_step_kernel(Ws w, int nparts, int C) {
   __shared__ double red[4][256];
   if (w.ctl->done) return;
   double s[4] = {0, 0, 0, 0};
+  for (int i = threadIdx.x; i < C; i += 256) s[0] += w.cost_cand[i];
   for (int i = threadIdx.x; i < nparts; i += 256)
-    for (int k = 0; k < 4; ++k) s[k] += w.part_F[4 * i + k];
+    for (int k = 1; k < 4; ++k) s[k] += w.part_F[4 * i + k];
   for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
@@ -2586,9 +2582,18 @@ __global__ __launch_bounds__(64) void control_kernel(Ws w, vgg_ba_options opt, i
   w.log[it] = li;
 }
 
+// Accepted step: the candidate becomes x, and its linearisation (cam_pass<CAND>) the one in reduce buffer 0 -- nothing is
+// evaluated again at the start of the next iteration.  Rejected step: the linearisation in buffer 0 stays; with several ranks
+// every rank holds its all-reduced value there, and the ranks other than 0 clear theirs, so that the SUM over the ranks
+// behind the next phase 0 gives it back exactly (x + 0 + ... + 0).
 __global__ void commit_kernel(Ws w, double* cam_q, double* cam_t, double* intr, double* pts, int C, int NI, int P) {
-  if (!w.ctl->accept) return;     // accept is cleared by control_kernel on every live iteration
+  const Ctl* ctl = w.ctl;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (!ctl->accept) {             // (accept is cleared by control_kernel on every live iteration)
+    if (ctl->world > 1 && ctl->rank != 0 && i < w.lin_count) w.lin[i] = 0.0;
+    return;
+  }
+  if (i < w.lin_count) w.lin[i] = w.lin_cand[i];
   if (i < (size_t)3 * P) pts[i] = w.cand_pts[i];
   if (i < (size_t)4 * C) cam_q[i] = w.cand_q[i];
   if (i < (size_t)3 * C) cam_t[i] = w.cand_t[i];
@@ -2781,12 +2786,14 @@ static inline int cam_split_for(int C, int O) {
   return s < 1 ? 1 : (s > kCamSplitMax ? kCamSplitMax : s);
 }
 
+// U_c, g_c, cost of the local observations at the parameters `dp` points to, into the buffer `w` points to: the start point
+// into reduce buffer 0 (vgg_ba_begin), the candidate into lin_cand (phase 2).  One kernel pair for both, so that the
+// linearisation an accepted candidate leaves behind is bit for bit the one a pass at the new x would compute.
 template <int KD>
-static void phase_linearize(const Launch& L) {
-  ProfScope ps(kProfLinearize, L.st);
+static void launch_linearize(const Launch& L, const DevProblem& dp, const Ws& w) {
   const int split = cam_split_for(L.d.C, L.d.O);
-  cam_pass_kernel<KD, 0><<<dim3(L.d.C, split), 256, 0, L.st>>>(L.dp, L.w);
-  cam_reduce_kernel<KD, 0><<<L.d.C, 64, 0, L.st>>>(L.dp, L.w, split, 0);
+  cam_pass_kernel<KD, 0><<<dim3(L.d.C, split), 256, 0, L.st>>>(dp, w);
+  cam_reduce_kernel<KD, 0><<<L.d.C, 64, 0, L.st>>>(dp, w, split, 0);
 }
 
 // one batch of Schur tiles: the off-diagonal launch, the diagonal launch, and the ordered sum of their chunks into
@@ -2971,13 +2978,13 @@ static int phase_step(const Launch& L) {
   cam_update_kernel<KD><<<div_up(d.C + 1, 64), 64, 0, L.st>>>(L.dp, L.w);
   {
     ProfScope ps(kProfPointStep, L.st);
-    const size_t cam_lds = sizeof(double) * 31 * (size_t)d.C;
+    const size_t cam_lds = sizeof(double) * 19 * (size_t)d.C;
     auto launch = [&](auto lpp) {
       constexpr int LPP = decltype(lpp)::value;
       const bool longt = long_tracks(LPP, L.d.P, L.d.O);
       auto go = [&](auto fy) {
         constexpr int FY = decltype(fy)::value;
-        const size_t lds = FY == 1 ? sizeof(double) * 18 * (size_t)d.C : cam_lds;
+        const size_t lds = FY == 1 ? sizeof(double) * 6 * (size_t)d.C : cam_lds;
         if (longt && LPP <= 32) {
           if (lds <= 64 * 1024) point_step_kernel<KD, true, LPP, (LPP <= 32), FY><<<L.wgB, 256, lds, L.st>>>(L.dp, L.w);
           else point_step_kernel<KD, false, LPP, (LPP <= 32), FY><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
@@ -2993,7 +3000,16 @@ static int phase_step(const Launch& L) {
     else if (L.lpp == 32) launch(std::integral_constant<int, 32>{});
     else launch(std::integral_constant<int, 64>{});
   }
-  reduce_step_kernel<<<1, 256, 0, L.st>>>(L.w, L.wgB);
+  {
+    // the candidate's cost and, should the step be accepted, the next linearisation (bench.py's cam_pass<linearize> slot)
+    ProfScope ps(kProfLinearize, L.st);
+    DevProblem dc = L.dp;
+    dc.cam_q = L.w.cand_q; dc.cam_t = L.w.cand_t; dc.intr = L.w.cand_intr; dc.pts = L.w.cand_pts;
+    Ws wc = L.w;
+    wc.U = L.w.U_cand; wc.g = L.w.g_cand; wc.costc = L.w.cost_cand;
+    launch_linearize<KD>(L, dc, wc);
+  }
+  reduce_step_kernel<<<1, 256, 0, L.st>>>(L.w, L.wgB, d.C);
   return VGG_OK;
 }
 
@@ -3003,6 +3019,7 @@ static void phase_update(const Launch& L) {
   size_t nmax = (size_t)3 * d.P;
   if ((size_t)4 * d.C > nmax) nmax = (size_t)4 * d.C;
   if ((size_t)4 * d.NI > nmax) nmax = (size_t)4 * d.NI;
+  if (L.w.lin_count > nmax) nmax = L.w.lin_count;
   commit_kernel<<<div_up((long)nmax, 256), 256, 0, L.st>>>(L.w, L.cam_q, L.cam_t, L.intr, L.pts, d.C, d.NI, d.P);
 }
 
@@ -3072,9 +3089,7 @@ static int dispatch_kd(int kd, Fn0 f0, Fn1 f1, Fn2 f2) {
 
 static int run_phase(const Launch& L, int phase) {
   switch (phase) {
-    case 0:
-      return dispatch_kd(L.d.kd, [&] { phase_linearize<0>(L); return VGG_OK; }, [&] { phase_linearize<1>(L); return VGG_OK; },
-                         [&] { phase_linearize<2>(L); return VGG_OK; });
+    case 0: return VGG_OK;          // (reduce buffer 0 was filled by vgg_ba_begin or, after an accepted step, by phase 3)
     case 1:
       return dispatch_kd(L.d.kd, [&] { phase_schur<0>(L); return VGG_OK; }, [&] { phase_schur<1>(L); return VGG_OK; },
                          [&] { phase_schur<2>(L); return VGG_OK; });
@@ -3220,6 +3235,9 @@ int vgg_ba_begin(const vgg_ba_problem* problem, const vgg_ba_options* options, v
   // strict upper one, so it stays zero -- reduce buffer 1 as include/vggsfm_amd.h describes it
   VGG_HIP_CHECK(hipMemsetAsync(L.w.sys, 0, sizeof(double) * L.w.sys_count, L.st));
   init_kernel<<<div_up(L.d.n_red > 0 ? L.d.n_red : 1, 256), 256, 0, L.st>>>(L.dp, L.w, L.opt, rank, world_size);
+  // the linearisation at the start point; every later one is cam_pass<CAND>'s of an accepted step
+  (void)dispatch_kd(L.d.kd, [&] { launch_linearize<0>(L, L.dp, L.w); return VGG_OK; },
+                    [&] { launch_linearize<1>(L, L.dp, L.w); return VGG_OK; }, [&] { launch_linearize<2>(L, L.dp, L.w); return VGG_OK; });
   VGG_LAUNCH_CHECK();
   return VGG_OK;
 }

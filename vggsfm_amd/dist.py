@@ -7,13 +7,16 @@ independent.  Every residual touches exactly one point, so V_p, g_p, the Schur c
 back-substitution of a point are rank-local; what couples the ranks is only the camera side:
 
   phase 0 LINEARIZE  local U_c = sum F^T F, g_c = sum F^T r, cost        -> all-reduce SUM  (C*(BD^2+BD+1) doubles)
+                     (computed by begin() at the start point, later by phase 2 at the candidate and kept by phase 3 if the
+                     step is accepted: phase 0 itself launches nothing)
   phase 1 SCHUR      local reduced system S, rhs of the rank's points     -> REDUCE-SCATTER + ALL-GATHER of the packed lower
                      local max |g_p|                                          triangle + rhs (n(n+1)/2 + n doubles: every rank
                                                                               sums 1/N of it, then the slices go round; on the
                                                                               point-to-point xGMI mesh that keeps all 7 links of
                                                                               a GPU busy); the local maxima ride in
                                                                               the gather (one slot per rank) -- no MAX collective
-  phase 2 STEP       every rank factors S redundantly, back-substitutes its points,
+  phase 2 STEP       every rank factors S redundantly, back-substitutes its points, evaluates the candidate camera-major
+                     (the next phase 0's terms if it is accepted),
                      local candidate cost / model change / step norm       -> all-reduce SUM  (4 doubles)
   phase 3 UPDATE     identical trust-region decision on every rank
 
