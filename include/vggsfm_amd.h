@@ -476,6 +476,29 @@ int vgg_reproj_draw(const uint8_t* images, const int64_t* img_off, const int32_t
                     const int64_t* grid_off, int frame_begin, int frame_end, int canvas_h, int canvas_w, int draw_radius,
                     const uint32_t* grid_obs, const uint32_t* color, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Point colours of the video path
+ *   VideoRunner._update_points_color   vggsfm/runners/video_runner.py:475-492
+ * All pointers are device memory.  The observation table is point-major: obs_point (O) int64 ascending (ties in
+ * ascending frame), obs_frame (O) int64, obs_uv (O,2) float32; O < 2^31, points 0 .. num_points-1.
+ *
+ * Gather, frame-major: rows row_begin .. row_end-1 of order (a permutation of 0 .. O-1 grouping the observations by
+ * frame) must be observations of frames frame_begin .. frame_end-1, and frames holds exactly those frames as
+ * (frame_end - frame_begin, 3, height, width) float32.  For each such observation o: u = floor(uv[0]), v = floor(uv[1])
+ * as int64; if v < height and u < width (no lower bound) it contributes images[f, :, v, u] (reverse: [f, :, u, v]), a
+ * negative index counting from the end as in Python.  gathered (O,4) float32 row o = (r, g, b, 1) when it contributes,
+ * else (0, 0, 0, 0).  An index still out of range after wrapping (the reference's IndexError), or a row whose frame lies
+ * outside the chunk: atomicMin(bad_obs, o), the row is written as not contributing.  The caller sets *bad_obs = INT32_MAX
+ * before the first chunk.  Every chunk writes only its own rows, so any split of the frames gives the same buffer. */
+int vgg_color_gather(const float* frames, int frame_begin, int frame_end, int height, int width, int reverse,
+                     const int64_t* order, long row_begin, long row_end, const int64_t* obs_frame, const float* obs_uv,
+                     long num_obs, float* gathered, int32_t* bad_obs, void* stream);
+/* Per point, after the gathers of every frame: rgb (P,3) float32 = the float32 sum of the contributing rows of gathered,
+ * in table order, divided by their count; (0, 0, 0) and has_color = 0 for a point without one (has_color (P) uint8,
+ * else 1).  point_ptr: workspace of num_points + 1 int64 (overwritten with the point-major row offsets).  Two launches. */
+int vgg_color_reduce(const int64_t* obs_point, long num_obs, long num_points, const float* gathered, int64_t* point_ptr,
+                     float* rgb, uint8_t* has_color, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

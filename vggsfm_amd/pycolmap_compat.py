@@ -548,11 +548,12 @@ class Reconstruction:
 
     @classmethod
     def from_frame_lists(cls, points3d_valid, valid_idx, extrinsics, intrinsics, xy, point3D_ids, frame_counts, image_size,
-                         shared_camera=False, camera_type="SIMPLE_PINHOLE", extra_params=None):
+                         shared_camera=False, camera_type="SIMPLE_PINHOLE", extra_params=None, colors=None):
         """The same model as :meth:`from_arrays` from observation LISTS the caller selected already (on the device:
         ``vggsfm_amd.utils.tensor_to_pycolmap.batch_matrix_to_pycolmap``): points3d_valid (n,3) = the kept tracks in track
         order, valid_idx (n,) their input track indices, xy (O,2) f64 / point3D_ids (O,) i64 frame-major (frame f owns the
-        next frame_counts[f] rows, tracks ascending inside a frame).  The per-image lists are views of xy / point3D_ids."""
+        next frame_counts[f] rows, tracks ascending inside a frame).  The per-image lists are views of xy / point3D_ids.
+        colors: (n,3) uint8 colours of the points (default 0)."""
         if camera_type not in CAMERA_MODEL_IDS:
             raise ValueError(f"Camera type {camera_type} is not supported yet")
         ext, K, size = _np(extrinsics), _np(intrinsics), _np(image_size).reshape(-1)
@@ -564,6 +565,8 @@ class Reconstruction:
         n = len(points3d_valid)
         rec._reserve(n)
         rec._xyz[:n], rec._alive[:n], rec._n = _np(points3d_valid), True, n
+        if colors is not None:
+            rec._rgb[:n] = np.asarray(colors).reshape(-1, 3)[:n].astype(np.uint8)
         off = np.concatenate([[0], np.cumsum(np.asarray(frame_counts, dtype=np.int64))])
         assert off[-1] == len(pid) == len(xy) and len(off) == S + 1
         camera = None

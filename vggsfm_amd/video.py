@@ -14,8 +14,11 @@
 
 All kernels underneath are the ones of the batch path (pose.hip, geometry.hip, triangulate.hip, ba.hip).
 """
+import math
+import os
 import random
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -368,3 +371,160 @@ class VideoGeometry:
         print("Running joint BA for the entire sequence:")
         self.joint_BA(0, T, normalize=True)
         return self.table
+
+    # ------------------------------------------------------------------ the output tail of VideoRunner.run
+    def update_points_color(self, images, reverse=False, frame_chunk=None):
+        """``_update_points_color`` (video_runner.py:475-492) with two HIP launches instead of the per-observation loop
+        (:func:`point_colors`).  images: the processed frames, float32 (1,T,3,H,W) or (T,3,H,W), on the device or in host
+        memory (streamed to the device `frame_chunk` frames at a time).  Sets ``table.rgb``; the per-point "has colour"
+        mask is kept in ``points_colored``.  Returns (rgb (P,3) float32, has_color (P,) bool)."""
+        rgb, has = point_colors(self.table, images, reverse=reverse, frame_chunk=frame_chunk)
+        self.table.rgb = rgb
+        self.points_colored = has
+        return rgb, has
+
+    def dicts_to_output(self, start_idx, end_idx, image_paths, crop_params, image_size, back_to_original_resolution=False,
+                        shift_point2d_to_original_res=False, shared_camera=True):
+        """``dicts_to_output`` (video_runner.py:249-308) with ``dicts_to_reconstruction(extract_color=True)`` (:543-604)
+        and ``build_camera_for_video`` (:1019-1049): the reference's ``predictions`` dict, its "reconstruction" a
+        ``pycolmap_compat.Reconstruction``.  image_size: the processed (W, H) (the reference's ``self.image_size``);
+        crop_params (1,T,>=4) or (T,>=4), of which frame 0's row serves the whole video (:102); image_paths: T paths,
+        whose base names the images get when `back_to_original_resolution`.  Only (start_idx, end_idx) = (0, T) is
+        supported, which is how the reference calls it.  Points keep their ids (+ 1), xyz rounded to float32 as the
+        reference's dicts hold them, colour round(rgb * 255) as uint8 for the points :meth:`update_points_color` coloured
+        and 0 for the others (the reference's last normalising joint BA leaves uint8 zeros); images 0..T-1 named
+        image_<idx> (before renaming), one camera id 0, points2D in ascending point id with the table's float32 uv."""
+        from .pycolmap_compat import CAMERA_MODEL_IDS, Reconstruction
+        from .runners import rename_colmap_recons_and_rescale_camera
+        from .utils.tensor_to_pycolmap import pycolmap_to_batch_matrix
+
+        t = self.table
+        T = int(t.extri.shape[0])
+        if (int(start_idx), int(end_idx)) != (0, T) or not bool(t.has_extri.all()):
+            raise ValueError(f"dicts_to_output covers every frame, (0, {T}) with all of them registered; got "
+                             f"({start_idx}, {end_idx})")
+        if self.camera_type not in CAMERA_MODEL_IDS:
+            raise NotImplementedError(f"Camera type {self.camera_type} not implemented")
+        if back_to_original_resolution and (image_paths is None or len(image_paths) < T or crop_params is None):
+            raise ValueError("back_to_original_resolution needs T image_paths and crop_params")
+        dev, P = self.device, t.num_points
+        W, H = (float(v) for v in (image_size.tolist() if torch.is_tensor(image_size) else image_size))
+        xyz = t.xyz.to(torch.float32)
+        has = getattr(self, "points_colored", None)
+        if has is None or has.shape[0] != P or t.rgb.shape[0] != P:
+            rgb = torch.zeros((P, 3), dtype=torch.float32, device=dev)
+        else:
+            rgb = torch.where(has[:, None], t.rgb.to(torch.float32), torch.zeros((), dtype=torch.float32, device=dev))
+        color = torch.round(rgb * 255).to(torch.uint8)          # np.round(rgb * 255): float32 product, half to even
+        # observation lists, frame-major with ascending point id inside a frame (the lists after a normalising joint BA)
+        order = torch.argsort(t.obs_frame, stable=True)
+        lists = torch.cat([t.obs_uv[order].to(torch.float64), (t.obs_point[order] + 1).to(torch.float64)[:, None]], 1)
+        counts = torch.bincount(t.obs_frame, minlength=T)
+        if counts.shape[0] > T:
+            raise ValueError("the table holds observations of frames past the last registered one")
+        lists, counts = lists.cpu().numpy(), counts.cpu().numpy()
+        K = torch.zeros((T, 3, 3), dtype=torch.float64)
+        intr = self.intrinsics[0].detach().to("cpu", torch.float64)
+        K[:, 0, 0], K[:, 0, 2], K[:, 1, 2] = intr[0, 0], intr[0, 2], intr[1, 2]   # [f, cx, cy] (build_camera_for_video)
+        ep = None
+        if self.camera_type == "SIMPLE_RADIAL":
+            ep = self.extra_params[0:1, 0:1].detach().to("cpu", torch.float64).expand(T, 1).numpy()
+        rec = Reconstruction.from_frame_lists(xyz.cpu().numpy(), np.arange(P), t.extri.cpu().numpy(), K.numpy(),
+                                              lists[:, :2], lists[:, 2].astype(np.int64), counts, np.array([W, H]),
+                                              shared_camera=True, camera_type=self.camera_type, extra_params=ep,
+                                              colors=color.cpu().numpy())
+        if back_to_original_resolution:
+            cp = torch.as_tensor(crop_params)
+            cp = cp if cp.dim() == 3 else cp[None]
+            rec = rename_colmap_recons_and_rescale_camera(rec, [os.path.basename(p) for p in image_paths],
+                                                          cp[:, 0:1].expand(-1, T, -1), H,
+                                                          shift_point2d_to_original_res=shift_point2d_to_original_res,
+                                                          shared_camera=shared_camera)
+        _, extrinsics, intrinsics, extra_params = pycolmap_to_batch_matrix(rec, dev, camera_type=self.camera_type)
+        return {"reconstruction": rec, "extrinsics_opencv": extrinsics, "intrinsics_opencv": intrinsics,
+                "extra_params": extra_params, "points3D": xyz, "points3D_rgb": rgb, "unproj_dense_points3D": None,
+                "valid_2D_mask": None, "pred_track": None, "pred_vis": None, "pred_score": None, "valid_tracks": None}
+
+    def finish(self, images, image_paths, crop_params, image_size, output_dir=None, shift_point2d_to_original_res=False,
+               shared_camera=True, frame_chunk=None):
+        """video_runner.py:193-206 after ``run``: colours, the output at the original resolution, and (with
+        `output_dir`) the model written to output_dir/sparse.  Returns the predictions."""
+        self.update_points_color(images, frame_chunk=frame_chunk)
+        T = int(self.table.extri.shape[0])
+        predictions = self.dicts_to_output(0, T, image_paths, crop_params, image_size, back_to_original_resolution=True,
+                                           shift_point2d_to_original_res=shift_point2d_to_original_res,
+                                           shared_camera=shared_camera)
+        if output_dir is not None:
+            predictions["reconstruction"].write(os.path.join(output_dir, "sparse"))
+        return predictions
+
+
+def point_colors(table, images, reverse=False, frame_chunk=None):
+    """``VideoRunner._update_points_color`` (video_runner.py:475-492) on a :class:`TrackTable`: per point the float32 mean
+    of images[0, f, :, floor(v), floor(u)] over its observations (f, (u, v)) with floor(v) < H and floor(u) < W, a
+    negative index counting from the end; reverse: images[0, f, :, floor(u), floor(v)] under the same test.  An index
+    out of range after that raises IndexError, as in the reference.  images: float32 (1,T,3,H,W) or (T,3,H,W), on the
+    device or in host memory; frames in host memory (or any frames with `frame_chunk`) go to the kernel `frame_chunk`
+    frames at a time (default 16 for host frames, all at once on the device).  The sum runs in table order (ascending
+    frame), so the result does not depend on the chunking or on where the frames live.
+    Returns (rgb (P,3) float32, has_color (P,) bool) on the table's device: rgb = 0 where has_color is False."""
+    import ctypes
+
+    if images.dim() == 5:
+        if images.shape[0] != 1:
+            raise ValueError(f"images: one video (1,T,3,H,W), got {tuple(images.shape)}")
+        images = images[0]
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"images: float32 (T,3,H,W) or (1,T,3,H,W), got {tuple(images.shape)} {images.dtype}")
+    dev = table.device
+    L = _lib.lib()
+    T, _, H, W = (int(v) for v in images.shape)
+    P, O = table.num_points, table.num_observations
+    rgb = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    has = torch.empty(P, dtype=torch.uint8, device=dev)
+    if P == 0:
+        return rgb, has.bool()
+    gathered = torch.empty((O, 4), dtype=torch.float32, device=dev)
+    bad = torch.full((1,), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+    if O:
+        counts = torch.bincount(table.obs_frame, minlength=T).cpu()
+        if counts.shape[0] > T:
+            f = int(torch.nonzero(counts[T:])[0, 0]) + T
+            raise IndexError(f"index {f} is out of bounds for dimension 0 with size {T} (an observation of frame {f})")
+        order = torch.argsort(table.obs_frame, stable=True)
+        row_ptr = [0] + torch.cumsum(counts, 0).tolist()
+        on_device = images.is_cuda
+        if on_device and dev.index is not None and images.device.index != dev.index:
+            raise ValueError(f"images live on {images.device}, the table on {dev}")
+        chunk = T if frame_chunk is None and on_device else int(frame_chunk or 16)
+        if chunk <= 0:
+            raise ValueError("frame_chunk must be positive")
+        _lib.require_gpu(table.obs_uv, gathered)
+        stream = _lib.stream_ptr()
+        staging = None
+        for f0 in range(0, T, chunk):
+            f1 = min(T, f0 + chunk)
+            if row_ptr[f1] == row_ptr[f0]:
+                continue
+            if on_device:
+                frames = images[f0:f1].contiguous()
+            else:
+                if staging is None:
+                    staging = torch.empty((chunk, 3, H, W), dtype=torch.float32, device=dev)
+                frames = staging[:f1 - f0]
+                frames.copy_(images[f0:f1], non_blocking=images.is_pinned())
+            _lib.check(L.vgg_color_gather(_lib.ptr(frames), ctypes.c_int(f0), ctypes.c_int(f1), ctypes.c_int(H),
+                                          ctypes.c_int(W), ctypes.c_int(1 if reverse else 0), _lib.ptr(order),
+                                          ctypes.c_long(row_ptr[f0]), ctypes.c_long(row_ptr[f1]), _lib.ptr(table.obs_frame),
+                                          _lib.ptr(table.obs_uv), ctypes.c_long(O), _lib.ptr(gathered), _lib.ptr(bad),
+                                          stream), "vgg_color_gather")
+    point_ptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
+    _lib.check(L.vgg_color_reduce(_lib.ptr(table.obs_point), ctypes.c_long(O), ctypes.c_long(P), _lib.ptr(gathered),
+                                  _lib.ptr(point_ptr), _lib.ptr(rgb), _lib.ptr(has), _lib.stream_ptr()), "vgg_color_reduce")
+    b = int(bad.item()) if O else 2 ** 31 - 1
+    if b != 2 ** 31 - 1:
+        p, f = int(table.obs_point[b]), int(table.obs_frame[b])
+        u, v = (float(x) for x in table.obs_uv[b].tolist())
+        raise IndexError(f"point {p}, frame {f}: pixel index (u, v) = ({math.floor(u)}, {math.floor(v)}) is out of range "
+                         f"for frames of {H} x {W}" + (" (reverse)" if reverse else ""))
+    return rgb, has.bool()
