@@ -347,8 +347,8 @@ int vgg_fmat_residuals(const double* points1, const double* points2, const uint8
  * Jacobians; cam_workgroups / point_workgroups (0 = automatic) -- total workgroups of the camera / point passes.  Every
  * combination computes the same iteration up to the order of its sums. */
 int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int point_workgroups);
-/* Where F^T (r - E h) (and, with a shared camera, the intrinsics border of the reduced system) come from: 2 (default;
- * VGG_TILE_RHS in the environment seeds it) = from the diagonal Schur tile launch for every block shape -- 6 x 6 blocks
+/* Where F^T (r - E h) (and, with a shared camera, the intrinsics border of the reduced system) come from: 2 (default)
+ * = from the diagonal Schur tile launch for every block shape -- 6 x 6 blocks
  * (shared or constant intrinsics, compressed factors): two wavefronts of a diagonal-tile workgroup multiply the staged segments
  * by a 3 x 3 per-point block on the side, + per-point sums of the point pass; 7 x 7 / 8 x 8 blocks (per-camera intrinsics, full
  * factors; round 6): every thread adds one tile row's products for two of a batch's entries -- no second camera-major evaluation
@@ -356,19 +356,6 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
  * round-4/5 behaviour); 0 = the camera pass always.  All compute the same system up to the order of its sums.  Requires
  * entries[e][0] = the entry's point. */
 int vgg_ba_set_tile_rhs(int enable);
-/* Where the back-substitution of the points (point_step_kernel) takes E^T F dy from, again with 6 x 6 tile blocks: 0 (default;
- * VGG_STEP_FACTORS seeds it) = a second evaluation of every projection and its Jacobians; 1 = from the compressed Schur
- * factors the point pass left in the segment buffer (one 96-byte record per observation; the model cost change's camera
- * share from the cameras' J^T J, J^T r); 2 = every other observation of a lane from its factor.  Same step up to rounding;
- * 1 and 2 measured slower on gfx950 (ba.hip, point_step_kernel) and are kept for measurements. */
-int vgg_ba_set_step_from_factors(int enable);
-/* Round-6 measurement switch for the off-diagonal Schur tile launch with 6 x 6 blocks (two launches per batch only): 0 (default;
- * VGG_TILE_DMA seeds it) = segments staged through registers from the compressed records; 1 = LDS-DMA (global_load_lds_dwordx4)
- * from an EXPANDED image of the segments, which a kernel of its own derives from the compressed records in front of the launch
- * (the workspace grows by 2304 bytes per segment: query vgg_ba_workspace_bytes AFTER setting the mode); 2 = 1 + a touch of the
- * lines of the batch after next.  Same tile sums up to the rounding of the rebuilt rows.  Measured, not adopted: ba.hip,
- * schur_tile_dma_kernel. */
-int vgg_ba_set_tile_dma(int mode);
 int vgg_ba_profile(int enable, int max_launches_per_kernel);
 int vgg_ba_profile_read(int kernel_id, double* total_ms, int* launches, int reset);
 
@@ -379,19 +366,18 @@ int vgg_ba_profile_read(int kernel_id, double* total_ms, int* launches, int rese
  * *device_fail (int32, device) is set non-zero on a non-positive pivot (2: a hand-off of the single-launch form timed out).
  * n >= 128 with b behind A runs as ONE launch (a workgroup per 64 x 64 tile, hand-offs through per-tile flags); the sums of
  * a tile are taken in a fixed order that depends on the structure passed (split / envelope) only: the factor is reproducible
- * run to run, and equal to the plain entry's up to the rounding of those sums (VGG_CHOL_CHAIN / VGG_CHOL_LEGACY in the
- * environment select the other forms for measurements). */
+ * run to run, and equal to the plain entry's up to the rounding of those sums. */
 size_t vgg_cholesky_workspace_bytes(int n);
 int vgg_cholesky_solve(double* A, double* b, int n, void* workspace, int32_t* device_fail, void* stream);
 /* the same with a block-diagonal leading part: A[i][j] = 0 for split_a <= i < split_a + split_b, j < split_a (exposed
- * for tests; see vgg_ba_problem.chol_split_a) */
+ * for tests; see vgg_ba_problem.chol_split_a).  The split is a scheduling hint of the single-launch form (b == A + n * n);
+ * with a separate b the system is factored in plain order. */
 int vgg_cholesky_solve_split(double* A, double* b, int n, int split_a, int split_b, void* workspace, int32_t* device_fail,
                              void* stream);
 /* the same with a row envelope: first_blk[r] (device, ceil(n / 64) entries) = first 64-column block in which rows
  * 64 r .. 64 r + 63 of A can be non-zero (see vgg_ba_problem.chol_first_blk); b must be stored directly behind A
  * (b == A + n * n) and n >= 128 for the envelope to be used (exposed for tests).  With an envelope the tiles are launched
- * in the order of their dependency depth and those outside it are not launched at all (one small set-up launch per call;
- * VGG_CHOL_TILE_MAP=0 in the environment keeps the (column, row) order for measurements) */
+ * in the order of their dependency depth and those outside it are not launched at all (one small set-up launch per call) */
 int vgg_cholesky_solve_envelope(double* A, double* b, int n, const int32_t* first_blk, void* workspace, int32_t* device_fail,
                                 void* stream);
 

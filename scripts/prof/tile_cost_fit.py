@@ -1,5 +1,5 @@
 """Calibration of the tile cost model (ba._entry_cost / TILE_FIXED_COST): per-workgroup cycle totals of the off-diagonal launch
-(library built with -DVGG_TILE_TRACE=1 -DVGG_TILE_PIPE=0 as vggsfm_amd/_variants/lib_tile_trace.so) against what the work list
+(library built with -DVGG_TILE_TRACE=1 as vggsfm_amd/_variants/lib_tile_trace.so) against what the work list
 says each workgroup executes -- batches, and matrix instructions of its busiest / mean wavefront -- by least squares:
     cycles(workgroup) ~ a * batches + b * matrix_instructions
 usage: VGGSFM_AMD_LIB=vggsfm_amd/_variants/lib_tile_trace.so python scripts/prof/tile_cost_fit.py"""

@@ -1,4 +1,4 @@
-// Where do the bytes of a global_load_lds_dwordx4 land?  (round-6 LDS-DMA experiment: csrc/ba.hip, schur_tile_dma_kernel)
+// Where do the bytes of a global_load_lds_dwordx4 land?  (round-6 LDS-DMA staging experiment of the Schur tile launch: docs/HISTORY.md)
 // Every lane reads the two doubles (1000 lane + 0, 1000 lane + 1) -- with lanes XOR 8 swapped on the source side in the second
 // test, and only lanes < 16 active in the third -- into one LDS buffer; the host prints which double sits at which LDS index.
 #include <hip/hip_runtime.h>

@@ -13,8 +13,6 @@ Then the contracts of the multi-GPU reduce buffers (include/vggsfm_amd.h, vgg_ba
 import ctypes
 import hashlib
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -223,28 +221,6 @@ IGNORE = {"chol_envelope": {3}}
 @pytest.mark.parametrize("name", list(CASES))
 def test_entry_on_poisoned_memory(name):
     _check_poisoned(CASES[name], IGNORE.get(name, ()))
-
-
-# --- Cholesky multi-launch path (VGG_CHOL_LEGACY=1 is read once per process) ---------------------------------------------
-LEGACY_CASES = ["chol_fused_n127", "chol_fused_n1202", "chol_fused_n4500", "ba_S17_separate", "ba_S33_merged"]
-
-
-def _legacy_main():
-    """Child process of test_legacy_cholesky_on_poisoned_memory."""
-    assert os.environ.get("VGG_CHOL_LEGACY") == "1"
-    for name in LEGACY_CASES:
-        with pytest.MonkeyPatch.context() as mp:
-            _memo_oracle(mp)
-            _check_poisoned(CASES[name], IGNORE.get(name, ()))
-        print("legacy ok:", name, flush=True)
-
-
-def test_legacy_cholesky_on_poisoned_memory():
-    env = dict(os.environ, VGG_CHOL_LEGACY="1")
-    r = subprocess.run([sys.executable, "-c", "import tests.test_gpu_poisoned_memory as m; m._legacy_main()"], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-6000:])
-    assert r.stdout.count("legacy ok:") == len(LEGACY_CASES)
 
 
 # --- reduce-buffer contracts -----------------------------------------------------------------------------------------------

@@ -47,9 +47,6 @@ constexpr int kGroup = 16;       // cameras per Schur tile side
 #ifndef VGG_DIAG_OCC
 #define VGG_DIAG_OCC 4      // wavefronts per SIMD of the diagonal Schur kernel (BD = 6)
 #endif
-#ifndef VGG_TILE_INTERLEAVE
-#define VGG_TILE_INTERLEAVE 1   // full-factor tiles: LDS writes of the next batch between the K steps of the current one
-#endif
 #ifndef VGG_DIAG_FULL_DEPTH
 #define VGG_DIAG_FULL_DEPTH 2   // staging register sets of the full-factor diagonal tile launch
 #endif
@@ -59,9 +56,6 @@ constexpr int kGroup = 16;       // cameras per Schur tile side
 #ifndef VGG_TRF_ABLATE
 #define VGG_TRF_ABLATE 0      // profiling builds, bits: 1 = no row products, 2 = no z loads, 4 = no store of the sums
 #endif
-#ifndef VGG_TRF_EARLY
-#define VGG_TRF_EARLY 2   // full-factor tile_rhs: row products behind K step VGG_TRF_EARLY - 1 of the batch (0: behind the batch)
-#endif
 #ifndef VGG_PP_OCC_SPLIT
 #define VGG_PP_OCC_SPLIT 3   // point_pass without the Y sweep: 158 VGPRs
 #endif
@@ -70,9 +64,6 @@ constexpr int kGroup = 16;       // cameras per Schur tile side
 #endif
 #ifndef VGG_PP_OCC
 #define VGG_PP_OCC 2
-#endif
-#ifndef VGG_PS_OCC_FY
-#define VGG_PS_OCC_FY 2      // point_step_kernel without the Jacobian sweep
 #endif
 #ifndef VGG_PS_OCC
 #define VGG_PS_OCC 2
@@ -150,11 +141,6 @@ struct Ws {  // device workspace carve-up (pointers into the caller's buffer)
   unsigned long long* split_off;   // split exchange: [2][n + 2] elements of part A / B in the rows above row i (i = n: the rhs; i = n + 1: the part's total)
   double* rz;                 // [ceil(C / 16)][96 x 3] rz_part summed over the chunks of a group's diagonal tile (tile_reduce_kernel)
   int tile_rhs;               // 1: cam_pass<RHS> is not launched, its sums come from the diagonal tile launch + point_pass
-  int step_from_factors;      // 1: point_step_kernel takes E^T F dy from the compressed Schur factors (no Jacobian sweep)
-  // round-6 A/B (vgg_ba_set_tile_dma): the off-diagonal tile launch stages by LDS-DMA from the EXPANDED image of the segments
-  double* Yx;                 // [num_segments + 1][3][96]: a segment as the tile kernels hold it in LDS (component-major rows)
-  size_t yx_bytes;
-  int tile_dma;
   // the linearisation at the candidate (cam_pass<CAND>, same layout as `lin`): carved behind everything else so that no
   // other buffer moves; commit_kernel copies it into `lin` when the step is accepted
   double* lin_cand;
@@ -179,12 +165,9 @@ static Dims make_dims(const vgg_ba_problem* pb) {
   return d;
 }
 
-// overrides of the automatic launch choices (vgg_ba_tuning; the environment variables seed them): 0 / -1 = automatic
-struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs, step_factors, tile_dma; };
-static Tuning g_tuning = [] {
-  auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-  return Tuning{env("VGG_LPP", 0), env("VGG_PP_LONGT", -1), env("VGG_CAM_WGS", 0), env("VGG_POINT_WGS", 0), env("VGG_TILE_RHS", 2), env("VGG_STEP_FACTORS", 0), env("VGG_TILE_DMA", 0)};
-}();
+// overrides of the automatic launch choices (vgg_ba_tuning, vgg_ba_set_tile_rhs): 0 / -1 = automatic
+struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs; };
+static Tuning g_tuning = {0, -1, 0, 0, 2};
 
 static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, void* base) {
   Ws w;
@@ -224,9 +207,6 @@ static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, 
   // + one all-zero segment behind the last real one (target of the tile kernel's loads past the end of a list)
   w.y_bytes = 8ull * ((size_t)(num_segments > 0 ? num_segments : 0) + 1) * kGroup * y_slot_doubles(d);
   w.Y = (double*)take(w.y_bytes);
-  w.yx_bytes = (g_tuning.tile_dma && (d.shared || d.kd == 0)) ? 8ull * ((size_t)(num_segments > 0 ? num_segments : 0) + 1) * kGroup * 18 : 0;
-  w.Yx = w.yx_bytes ? (double*)take(w.yx_bytes) : nullptr;
-  w.tile_dma = 0;
   w.chol_inv = (double*)take(cholesky_workspace_bytes(d.n_red));
   {
     const size_t bdt = d.shared ? 6 : d.BDp;
@@ -659,12 +639,12 @@ __global__ __launch_bounds__(256) void prep_kernel(DevProblem pb, Ws w, vgg_ba_o
   }
 }
 
-// VGG_SPLIT_POINT_PASS=1 in the environment selects the split form of the point pass -- wave-per-point reductions without
-// the Y sweep (158 VGPRs, 3 wavefronts per SIMD) + y_write_kernel (thread per observation, 127 VGPRs).  Built and measured
-// in round 2 (c3): 0.25 + 0.47 ms against 0.43 ms for the fused pass -- the reductions did not speed up with the third
-// wavefront and a thread-per-observation writer without the LDS camera table is slower than the in-wave sweep -- so
-// the fused pass stays the default.
-// Lanes per point of the point passes from the mean track length (VGG_LPP=8|16|32|64 overrides).  A point's lanes share
+// The split form of the point pass -- wave-per-point reductions without the Y sweep (158 VGPRs, 3 wavefronts per SIMD) +
+// y_write_kernel (thread per observation, 127 VGPRs) -- was built and measured in round 2 (c3): 0.25 + 0.47 ms against
+// 0.43 ms for the fused pass -- the reductions did not speed up with the third wavefront and a thread-per-observation
+// writer without the LDS camera table is slower than the in-wave sweep -- so the fused pass is the one in the tree
+// (DESIGN.md section 6).
+// Lanes per point of the point passes from the mean track length (vgg_ba_tuning overrides).  A point's lanes share
 // its serial work (reductions, 3 x 3 factorisation), which outweighs the sweeps over its observations up to ~70 of them:
 // measured per LM iteration, point_pass + point_step -- c2 (mean 12.5 observations) 64: 0.112, 32: 0.075, 16: 0.065,
 // 8: 0.059 ms; c3 (mean 50) 64: 0.674, 32: 0.549, 16: 0.499, 8: 0.535 ms; one c4 shard (mean 100) 32: 0.509, 16: 0.544 ms.
@@ -1154,18 +1134,6 @@ __device__ __forceinline__ double dpp_swap_xor1(double v) {
 #if VGG_TILE_TRACE
 __device__ long long g_tile_trace[2048 * 4 * 8];   // [workgroup][wave][batches, fetch+issue, matrix phase, LDS write phase, barrier wait, total]
 #endif
-#ifndef VGG_TILE_PRIO
-#define VGG_TILE_PRIO 2              // wave priority: 2 = raised outside the matrix phase (staging, LDS writes, barrier): a wavefront
-#endif                               // gets back to its matrix instructions sooner (round 3: off-diagonal launch 0.620 -> 0.606 ms); 1 = raised inside
-#ifndef VGG_DIAG_PARITY
-#define VGG_DIAG_PARITY 1           // diagonal tiles: sub-tiles dealt to the wavefronts by parity class (0: every fourth, round 3)
-#endif
-#ifndef VGG_TILE_EARLY_WRITE
-#define VGG_TILE_EARLY_WRITE 1      // pipelined off-diagonal step: the LDS writes of batch b + 1 in front of batch b's matrix instructions (0: behind them)
-#endif
-#ifndef VGG_TILE_PIPE
-#define VGG_TILE_PIPE 1             // compressed off-diagonal tiles: the last K step of a batch behind its barrier (round 5; 0: plain order)
-#endif
 #ifndef VGG_NO_SKIP
 #define VGG_NO_SKIP 0               // profiling builds: 1 = every sub-tile of every batch runs (no presence skipping)
 #endif
@@ -1241,7 +1209,7 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
   // wavefronts per SIMD.  Scales and constant-parameter masks are applied by assemble_kernel, like tile_reduce_kernel does
   // for the tile sums.
   constexpr bool TR = CY && DIAG;
-  constexpr bool INTERLEAVE = VGG_TILE_INTERLEAVE && !CY;
+  constexpr bool INTERLEAVE = !CY;   // full-factor tiles: LDS writes of the next batch between the K steps of the current one
   const bool trhs = TR && w.tile_rhs != 0;
   // tile_rhs with FULL factors (7 x 7 / 8 x 8 blocks: per-camera intrinsics, round 6).  All four wavefronts stage here, so
   // there are no helpers: once a batch is in LDS, thread t adds the products of tile row t % R for two of the batch's four
@@ -1396,11 +1364,9 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
 #endif
       VGG_TT(tr_issue)
 #if VGG_ABLATE != 1
-#if VGG_TILE_PRIO == 1                            // experiment: matrix phase at raised wave priority
-      __builtin_amdgcn_s_setprio(2);
-#elif VGG_TILE_PRIO == 2                          // experiment: staging phases at raised wave priority
+      // wave priority raised outside the matrix phase (staging, LDS writes, barrier): a wavefront gets back to its matrix
+      // instructions sooner (round 3: off-diagonal launch 0.620 -> 0.606 ms)
       __builtin_amdgcn_s_setprio(0);
-#endif
       auto rhs_rows = [&](int buf) __attribute__((always_inline)) {
         if (trf && tid < 2 * R && !(VGG_TRF_ABLATE & 1)) {
           const int rrow = tid % R, half = tid / R;
@@ -1425,9 +1391,8 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
 #endif
         // (full-factor tile_rhs: the row's products are read and added BETWEEN K steps 1 and 2, under the matrix instructions
         //  of the batch -- behind the last one they were a tail of twelve exposed LDS reads per wavefront in front of the barrier)
-        if constexpr (TRF && VGG_TRF_EARLY) { if (k == VGG_TRF_EARLY - 1) rhs_rows(buf); }
+        if constexpr (TRF) { if (k == 1) rhs_rows(buf); }
       });
-      if constexpr (TRF && !VGG_TRF_EARLY) rhs_rows(buf);
       if constexpr (TR && HELPER) {
         if (trhs) {
           const int rrow = tid & 127;                 // (wavefront 2: tile rows 0..63, wavefront 3: 64..95)
@@ -1447,11 +1412,7 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
           }
         }
       }
-#if VGG_TILE_PRIO == 1
-      __builtin_amdgcn_s_setprio(0);
-#elif VGG_TILE_PRIO == 2
       __builtin_amdgcn_s_setprio(3);
-#endif
 #endif
       VGG_TT(tr_mfma)
       qmask = qmask_next;
@@ -1506,7 +1467,7 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
       bitsA[i] = block_slot_bits<BD>(wr + 2 * i);
       bitsB[i] = block_slot_bits<BD>(wc + 2 * i) << 16;
     }
-#if VGG_TILE_PIPE && !VGG_ABLATE && !VGG_TILE_TRACE     // (ablation / trace builds take sweep(), which carries their hooks)
+#if !VGG_ABLATE && !VGG_TILE_TRACE    // (ablation / trace builds take sweep(), which carries their hooks)
     if constexpr (CY) {
       // PIPELINED BARRIER (round 5, compressed 6 x 6 off-diagonal tiles): the LAST K step of a batch is issued BEHIND the
       // batch's barrier.  Per step:  [loads of b+DEPTH] [K steps 0, 1 of b; operands of K step 2 fetched] [LDS image of b+1]
@@ -1556,12 +1517,10 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
         issue_loads(sv_load, seg_next, valid_next);
         seg_next = seg_after;
         valid_next = seg_valid(ebase(b + DEPTH + 1));
-#if VGG_TILE_EARLY_WRITE
         // the LDS image of batch b + 1 is written FIRST: buffer buf^1 is free since barrier(b - 1) -- its last readers fetched
         // K step 2 of batch b - 1 in front of that barrier -- so the writes have landed long before this step's barrier and
         // its lgkmcnt(0) costs nothing (same-box A/B profiles/r05_ab_tile_pipe_c3.jsonl: 0.531 -> 0.521 ms)
         write_lds(sv_write, buf ^ 1);
-#endif
         __builtin_amdgcn_s_setprio(0);
         on = skip_bits(qmask);
         fetch(1 - P, buf, 1); pin(P);
@@ -1572,9 +1531,6 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
         __builtin_amdgcn_s_setprio(3);
         qmask = qmask_next;
         qmask_next = load_quad_mask(ebase(b + 2));
-#if !VGG_TILE_EARLY_WRITE
-        write_lds(sv_write, buf ^ 1);
-#endif
         __syncthreads();
         fetch(1 - P, buf ^ 1, 0);                     // K step 0 of batch b + 1 (stale bytes behind the last batch: never used)
         __builtin_amdgcn_s_setprio(0);
@@ -1652,7 +1608,6 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
       for (int j = 0; j < NH; ++j)
         if (wr + 2 * i < NT && wc + 2 * j < NT) store_subtile(wr + 2 * i, wc + 2 * j, acc[i][j]);
   } else {
-#if VGG_DIAG_PARITY
     // diagonal tile (A == B, symmetric): only the NT (NT + 1) / 2 sub-tiles of the lower triangle are computed.  Round 4: a
     // wavefront owns a PARITY CLASS of them -- rows wr + 2 i, columns wc + 2 j, row block >= column block -- like the
     // off-diagonal variant, instead of every fourth one of the row-by-row enumeration: its sub-tiles then share their row
@@ -1723,54 +1678,6 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
         if (TR && j > i) continue;
         if (lower & (1u << (NH * i + j))) store_subtile(wr + 2 * i, wc + 2 * j, acc[i][j]);
       }
-#else
-    // diagonal tile (A == B, symmetric): only the NT (NT + 1) / 2 sub-tiles of the lower triangle are computed;
-    // they are enumerated row by row and dealt round-robin to the 4 waves (wave-uniform scalar tables); skipped like
-    // the off-diagonal ones when the quad has no camera in the rows or in the columns of the sub-tile
-    constexpr int NL = NT * (NT + 1) / 2;
-    constexpr int PER = (NL + 3) / 4;
-    static_assert(PER <= NH * NH, "accumulators");
-    const int nmine = __builtin_amdgcn_readfirstlane((NL - wave + 3) / 4);
-    int rbs[PER], cbs[PER], offA[PER], offB[PER];
-    uint32_t bitsR[PER], bitsC[PER];
-    {
-      int rb = 0, cb = 0;                           // walk to sub-tile `wave`
-      for (int t = 0; t < wave; ++t) { if (cb == rb) { ++rb; cb = 0; } else ++cb; }
-#pragma unroll
-      for (int t = 0; t < PER; ++t) {
-        rbs[t] = min(rb, NT - 1); cbs[t] = min(cb, NT - 1);
-        offA[t] = kbase + ((16 * rbs[t] + li) ^ swz); offB[t] = kbase + ((16 * cbs[t] + li) ^ swz);
-        bitsR[t] = (t < nmine) ? block_slot_bits<BD>(rbs[t]) : 0u;
-        bitsC[t] = (t < nmine) ? block_slot_bits<BD>(cbs[t]) : 0u;
-        for (int u = 0; u < 4; ++u) { if (cb == rb) { ++rb; cb = 0; } else ++cb; }
-      }
-    }
-    sweep([&](int buf, uint32_t qm, auto&& wr) {
-      const double* As = ops + (size_t)(buf * SIDES) * 4 * SEG;
-      uint32_t on = 0u;                             // bit t: sub-tile t of this wavefront has a camera in its rows and in its columns
-#pragma unroll
-      for (int t = 0; t < PER; ++t) on |= (((qm & bitsR[t]) != 0 && (qm & bitsC[t]) != 0) ? 1u : 0u) << t;
-      on = VGG_NO_SKIP ? ((1u << nmine) - 1u) : (uint32_t)__builtin_amdgcn_readfirstlane((int)on);
-      // (a sub-tile's row and column operands are fetched per K step, right in front of its matrix instruction: the diagonal
-      //  launch runs at four workgroups per CU and has no registers for a second operand set)
-#pragma unroll
-      for (int ks = 0; ks < 3; ++ks) {
-        uint32_t m = on;
-        asm volatile("" : "+s"(m));                 // (keeps the tests scalar bit tests; see the off-diagonal variant)
-        double a[PER], bq[PER];
-#pragma unroll
-        for (int t = 0; t < PER; ++t) { a[t] = As[offA[t] + ks * R]; bq[t] = As[offB[t] + ks * R]; }
-#pragma unroll
-        for (int t = 0; t < PER; ++t)
-          if (m & (1u << t))
-            acc[t / NH][t % NH] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], bq[t], acc[t / NH][t % NH], 0, 0, 0);
-        wr(ks);
-      }
-    });
-#pragma unroll
-    for (int t = 0; t < PER; ++t)
-      if (t < nmine) store_subtile(rbs[t], cbs[t], acc[t / NH][t % NH]);
-#endif
     if constexpr (TR && HELPER) {
       if (trhs) {                                     // the chunk's 96 x 3 block, a lane per tile row
         const int rrow = tid & 127;
@@ -1801,7 +1708,7 @@ __global__ __launch_bounds__(256, (BD == 6 ? (DIAG ? VGG_DIAG_OCC : VGG_OFFDIAG_
   const int chunk = chunk0 + blockIdx.x;
   schur_tile_body<BD, DIAG>(w, chunk_desc, entries, chunk, zero_seg, ops);
 }
-// ... or ONE launch for both (vgg_ba_tuning / VGG_TILE_MERGED): the diagonal tiles then sweep the points together with the
+// ... or ONE launch for both (vgg_ba_problem::merged_tile_launch): the diagonal tiles then sweep the points together with the
 // off-diagonal ones and find the segments those have just brought into the Infinity Cache
 template <int BD>
 __global__ __launch_bounds__(256, (BD == 6 ? VGG_OFFDIAG_OCC : 2)) void schur_tile_merged_kernel(Ws w, const int32_t* __restrict__ chunk_desc,
@@ -1813,223 +1720,6 @@ __global__ __launch_bounds__(256, (BD == 6 ? VGG_OFFDIAG_OCC : 2)) void schur_ti
   else schur_tile_body<BD, false>(w, chunk_desc, entries, chunk, zero_seg, ops);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// Round-6 A/B (vgg_ba_set_tile_dma): the off-diagonal launch of 6 x 6 tiles with LDS-DMA staging in
-// today's three-workgroups-per-CU shape.  The segments are read from their EXPANDED image Yx[seg][component][96 rows] -- what
-// schur_tile_body rebuilds from the compressed records on the way into LDS (12 DPP moves, 18 fp64 operations, 19 selects and six
-// ds_writes per lane and batch) -- by global_load_lds_dwordx4: 1 KB per wavefront instruction, straight into the LDS image, no
-// staging registers, no write phase.  The XOR swizzle of the odd entries sits on the SOURCE address (the destination of an
-// LDS-DMA instruction is lane-linear), the operand reads are those of schur_tile_body.
-// Two LDS buffers (three would not fit three workgroups per CU: 3 x 18 KB each), so the image of batch b + 1 is requested
-// behind barrier(b - 1) and has ONE matrix phase to land; mode 2 adds a touch of batch b + 2's lines (one dword load per 128
-// bytes) so that the DMA finds them in the L2.  For the measurement the expanded image is produced by a kernel of its own from
-// the compressed records (expand_segments_kernel, timed apart); in a product form point_pass would write it.
-// MEASURED, NOT ADOPTED (profiles/r06_ab_tile_ldsdma_c3.jsonl, configs[2], same box, two rounds, sums bit-identical to the
-// register-staged launch at equal chunking): register staging 0.528-0.532 ms; LDS-DMA at three workgroups per CU 0.559-0.565;
-// at FOUR per CU (the kernel needs 114 registers and 36 KB: it fits) 0.516-0.525; with the touch 0.66-0.72; with the last K step
-// behind the barrier (-DVGG_DMA_PIPE) 2.3.  The write phase is gone, but six DMA instructions per wavefront and batch cost
-// their own issue time (the guide: 60-185 cycles a piece next to matrix instructions) and the image has one matrix phase to land
-// in front of a vmcnt(0) + barrier; the -1..2 % of the best variant is less than the 0.24 GB per iteration the expanded image
-// would add to point_pass' writes (0.33 ms for the stand-alone expansion).  Closed.
-__global__ __launch_bounds__(256) void expand_segments_kernel(Ws w, int num_segments) {
-  if (w.ctl->done) return;
-  const size_t slot = (size_t)blockIdx.x * 256 + threadIdx.x;            // (segment, camera slot)
-  if (slot >= ((size_t)num_segments + 1) * kGroup) return;
-  const size_t seg = slot / kGroup;
-  const int sl = (int)(slot - seg * kGroup);
-  const double* rec = w.Y + slot * kYc;                                 // N (3 x 3, row-major), 2 a
-  double m[kYc];
-#pragma unroll
-  for (int i = 0; i < kYc; ++i) m[i] = rec[i];
-  double* dst = w.Yx + seg * (kGroup * 18) + 6 * sl;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double n0 = m[k], n1 = m[3 + k], n2 = m[6 + k];
-    // rows 0..2 = (2 a) x N[:, k] with the operations of schur_tile_body's rebuild, rows 3..5 = N[:, k]
-    dst[k * 96 + 0] = m[10] * n2 - m[11] * n1;
-    dst[k * 96 + 1] = m[11] * n0 - m[9] * n2;
-    dst[k * 96 + 2] = m[9] * n1 - m[10] * n0;
-    dst[k * 96 + 3] = n0; dst[k * 96 + 4] = n1; dst[k * 96 + 5] = n2;
-  }
-}
-
-#ifndef VGG_DMA_PIPE
-#define VGG_DMA_PIPE 0               // 1: the last K step of a batch behind its barrier, as schur_tile_body's pipelined order
-#endif
-template <int MODE>
-__global__ __launch_bounds__(256, VGG_OFFDIAG_OCC) void schur_tile_dma_kernel(Ws w, const int32_t* __restrict__ chunk_desc,
-                                                                              const int32_t* __restrict__ entries, int chunk0, int zero_seg) {
-  constexpr int BD = 6, R = kGroup * BD, SEG = 3 * R, NT = R / 16, NH = (NT + 1) / 2, SWZ = 16;
-  static_assert((SEG * 8) % 256 == 0, "swizzle");
-  __shared__ __attribute__((aligned(16))) double ops[2 * 2 * 4 * SEG];
-  if (w.ctl->done) return;
-  const int chunk = chunk0 + blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int e0 = chunk_desc[6 * chunk + 2], e1 = chunk_desc[6 * chunk + 3];
-  const int cj = chunk_desc[6 * chunk + 4], cJ = chunk_desc[6 * chunk + 5];
-  constexpr int BPS = kSub / 4;
-  const int nsub = (e1 - e0 + kSub - 1) / kSub;
-  const int nb = ((nsub - cj + cJ - 1) / cJ) * BPS;
-  auto ebase = [&](int b) -> int { return e0 + ((b / BPS) * cJ + cj) * kSub + (b % BPS) * 4; };
-  f64x4_t acc[NH][NH];
-#pragma unroll
-  for (int i = 0; i < NH; ++i)
-#pragma unroll
-    for (int j = 0; j < NH; ++j) acc[i][j] = (f64x4_t){0.0, 0.0, 0.0, 0.0};
-  // wavefront `wave` brings in the two segments of entry `wave` of a batch: 144 sixteen-byte pieces each = two full
-  // instructions + one of 16 lanes.  Piece y of the LDS image holds piece y ^ 8 of the segment when the entry is odd.
-  const char* Yx = reinterpret_cast<const char*>(w.Yx);
-  const int lane_off = ((lane ^ ((wave & 1) * (SWZ / 2))) * 16);
-  auto seg_of = [&](int b, int side) -> int {
-    const int e = ebase(b) + wave;
-    return (e < e1) ? entries[4 * (size_t)e + 1 + side] : zero_seg;
-  };
-  // (the segment indices of a batch are scalar loads issued one batch ahead: no round trip in front of the DMA)
-  int seg_nextA = seg_of(0, 0), seg_nextB = seg_of(0, 1);
-  auto issue_dma = [&](int b, int buf) __attribute__((always_inline)) {
-    const int segs[2] = {seg_nextA, seg_nextB};
-    seg_nextA = seg_of(b + 1, 0); seg_nextB = seg_of(b + 1, 1);
-#pragma unroll
-    for (int side = 0; side < 2; ++side) {
-      const char* src = Yx + (size_t)segs[side] * (SEG * 8) + lane_off;
-      double* dst = ops + (size_t)((buf * 2 + side) * 4 + wave) * SEG;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + 128), 16, 0, 0);
-      // the 16-lane tail: NOT behind a lane condition -- the compiler duplicates the neighbouring DMA statements into the two arms
-      // of such a branch and merges their tails with the LDS destination as a per-lane value (its readfirstlane then serves one
-      // arm: batch 0 of every chunk got side B's pieces from the wrong place).  All lanes run the statement; the execution mask
-      // is narrowed inside it (M0 = the wave-uniform LDS byte address, written in the statement that reads it).
-      {
-        const unsigned lds_tail = (unsigned)__builtin_amdgcn_readfirstlane((int)(uintptr_t)(__attribute__((address_space(3))) void*)(dst + 256));
-        const char* gtail = src + 2048;
-        unsigned long long keep;
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 0xffff\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off\n\ts_mov_b64 exec, %0"
-                     : "=&s"(keep) : "v"(gtail), "s"(lds_tail) : "memory");
-      }
-    }
-  };
-  // (mode 2) one dword of every 128-byte line of the two segments of batch b: lanes 0..17 side A, 32..49 side B
-  auto touch = [&](int b) -> int {
-    int v = 0;
-    if constexpr (MODE == 2) {
-      const int sub = lane & 31;
-      if (sub < 18) {
-        const char* src = Yx + (size_t)seg_of(b, lane >> 5) * (SEG * 8) + sub * 128;
-        asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(src) : "memory");
-      }
-    }
-    return v;
-  };
-  const int li = lane & 15, lk = lane >> 4;
-  const int kbase = lk * SEG, swz = (lk & 1) * SWZ;
-  auto load_quad_mask = [&](int eb) -> uint32_t { return (uint32_t)entries[4 * (size_t)min(eb, e1 - 1) + 3]; };
-  const int wr = wave >> 1, wc = wave & 1;
-  int rowoffA[NH], rowoffB[NH];
-  uint32_t bitsA[NH], bitsB[NH];
-#pragma unroll
-  for (int i = 0; i < NH; ++i) {
-    rowoffA[i] = kbase + ((16 * min(wr + 2 * i, NT - 1) + li) ^ swz);
-    rowoffB[i] = kbase + ((16 * min(wc + 2 * i, NT - 1) + li) ^ swz);
-    bitsA[i] = block_slot_bits<BD>(wr + 2 * i);
-    bitsB[i] = block_slot_bits<BD>(wc + 2 * i) << 16;
-  }
-  double a[2][NH], bq[2][NH];
-  auto fetch = [&](int set, int buf, int ks) __attribute__((always_inline)) {
-    const double* As = ops + (size_t)(buf * 2) * 4 * SEG;
-    const double* Bs = ops + (size_t)(buf * 2 + 1) * 4 * SEG;
-#pragma unroll
-    for (int i = 0; i < NH; ++i) { a[set][i] = As[rowoffA[i] + ks * R]; bq[set][i] = Bs[rowoffB[i] + ks * R]; }
-  };
-  auto pin = [&](int set) __attribute__((always_inline)) {
-    static_assert(NH == 3, "operand sets");
-    asm volatile("" : "+v"(a[set][0]), "+v"(a[set][1]), "+v"(a[set][2]), "+v"(bq[set][0]), "+v"(bq[set][1]), "+v"(bq[set][2]));
-  };
-  uint32_t on = 0u;
-  auto skip_bits = [&](uint32_t qm) -> uint32_t {
-    uint32_t colm = 0u, o = 0u;
-#pragma unroll
-    for (int j = 0; j < NH; ++j) colm |= ((qm & bitsB[j]) != 0 ? 1u : 0u) << j;
-#pragma unroll
-    for (int i = 0; i < NH; ++i) o |= ((qm & bitsA[i]) != 0 ? colm : 0u) << (NH * i);
-    return VGG_NO_SKIP ? 0xFFFFFFFFu : (uint32_t)__builtin_amdgcn_readfirstlane((int)o);
-  };
-  auto group = [&](int set) __attribute__((always_inline)) {
-    uint32_t m = on;
-    asm volatile("" : "+s"(m));
-#pragma unroll
-    for (int i = 0; i < NH; ++i)
-#pragma unroll
-      for (int j = 0; j < NH; ++j)
-        if (m & (1u << (NH * i + j))) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[set][i], bq[set][j], acc[i][j], 0, 0, 0);
-  };
-  uint32_t qmask = load_quad_mask(ebase(0)), qmask_next = load_quad_mask(ebase(1));
-  issue_dma(0, 0);
-  int tv = touch(1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();                                  // (the compiler puts the vmcnt(0) of the LDS-DMA in front of it)
-  asm volatile("" :: "v"(tv));
-#if VGG_DMA_PIPE
-  fetch(0, 0, 0);
-#endif
-  for (int b = 0; b < nb; ++b) {
-    const int buf = b & 1;
-    issue_dma(b + 1, buf ^ 1);                      // buffer buf^1: its last readers (batch b - 1) finished in front of barrier(b - 1)
-    tv = touch(b + 2);
-    on = skip_bits(qmask);
-#if VGG_DMA_PIPE
-    // (operand set P = b & 1 holds K step 0 of batch b; the sets alternate roles from batch to batch -- but the set index must be
-    //  a compile-time constant, so the loop body is written for both parities)
-    if (buf == 0) {
-      fetch(1, buf, 1); pin(0); group(0);
-      fetch(0, buf, 2); pin(1); group(1);
-      pin(0);
-      qmask = qmask_next; qmask_next = load_quad_mask(ebase(b + 2));
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the tail pieces are asm statements: not in the compiler's count)
-      __syncthreads();
-      asm volatile("" :: "v"(tv));
-      fetch(1, buf ^ 1, 0);
-      pin(0); group(0);
-    } else {
-      fetch(0, buf, 1); pin(1); group(1);
-      fetch(1, buf, 2); pin(0); group(0);
-      pin(1);
-      qmask = qmask_next; qmask_next = load_quad_mask(ebase(b + 2));
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the tail pieces are asm statements: not in the compiler's count)
-      __syncthreads();
-      asm volatile("" :: "v"(tv));
-      fetch(0, buf ^ 1, 0);
-      pin(1); group(1);
-    }
-#else
-    fetch(0, buf, 0);
-    fetch(1, buf, 1); pin(0); group(0);
-    fetch(0, buf, 2); pin(1); group(1);
-    pin(0); group(0);
-    qmask = qmask_next; qmask_next = load_quad_mask(ebase(b + 2));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    asm volatile("" :: "v"(tv));
-#endif
-  }
-  double* part = w.tile_part + (size_t)chunk * R * R;
-#pragma unroll
-  for (int i = 0; i < NH; ++i)
-#pragma unroll
-    for (int j = 0; j < NH; ++j)
-      if (wr + 2 * i < NT && wc + 2 * j < NT) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) part[(size_t)(16 * (wr + 2 * i) + lk + 4 * reg) * R + 16 * (wc + 2 * j) + li] = acc[i][j][reg];
-      }
-}
-
-// (Second formulation, commit a638f73, taken out again: WAVE SPECIALISATION -- five wavefronts per workgroup, four consumers that do
-//  nothing but [operand reads, matrix instructions, barrier] and one producer that issues the 18 one-KB DMA pieces of the next
-//  batch: sums bit-identical, 0.956 ms against 0.529 -- one producer cannot feed four consumers through two LDS buffers, and a
-//  third buffer does not fit three workgroups per CU.  profiles/r06_ab_tile_ldsdma_c3.jsonl.)
 // S[(cI,a,i),(cJ,b,j)] = - sum over the chunks of tile (gI,gJ) of the partial tiles (plain stores: every
 // element of S outside the per-camera diagonal terms belongs to exactly one (tile, element)).
 // grid = (R*R/256, num_tiles): one element per thread, chunks summed in order.
@@ -2303,57 +1993,21 @@ __global__ void cam_update_kernel(DevProblem pb, Ws w) {
     const int np = (d.model == kSimpleRadial) ? 4 : 3;
     for (int k = 0; k < 4; ++k) { w.cand_intr[4 * a + k] = in4[k]; if (intr_var && k < np) xn += pb.intr[4 * a + k] * pb.intr[4 * a + k]; }
   }
-  // Model cost change, the part that is a function of the camera-side step alone (compressed Schur factors: point_step_kernel
-  // no longer re-evaluates the Jacobians): sum over the observations of [F dy . r - |F dy|^2 / 2] = sum over the cameras of
-  // dy_c . g_c - dy_c^T U_c dy_c / 2, with U_c = sum F^T F and g_c = sum F^T r of the linearisation in place (cam_pass
-  // <linearize>, all-reduced over the ranks) and dy_c the camera's pose step followed by the step of its intrinsics block.
-  double mc = 0.0;
-  if (c < d.C && w.step_from_factors) {
-    constexpr int BD = 6 + KD;
-    double dv[BD];
-    for (int k = 0; k < 6; ++k) dv[k] = w.active[6 * c + k] ? w.scale_c[6 * c + k] * w.rhs[6 * c + k] : 0.0;
-    const int ai = d.shared ? 0 : c;
-    for (int k = 0; k < KD; ++k) { const int j = 6 * d.C + KD * ai + k; dv[6 + k] = w.active[j] ? w.scale_c[j] * w.rhs[j] : 0.0; }
-    const double* U = w.U + (size_t)c * BD * BD;
-    const double* g = w.g + (size_t)c * BD;
-    double lin = 0.0, quad = 0.0;
-    for (int i = 0; i < BD; ++i) {
-      double ui = 0.0;
-      for (int k = 0; k < BD; ++k) ui += U[i * BD + k] * dv[k];
-      quad += dv[i] * ui;
-      lin += dv[i] * g[i];
-    }
-    mc = lin - 0.5 * quad;
-  }
+  // (no camera-side share of the model cost change: point_step_kernel sums it observation by observation)
   w.cam_part[3 * c] = step;
   w.cam_part[3 * c + 1] = xn;
-  w.cam_part[3 * c + 2] = mc;
+  w.cam_part[3 * c + 2] = 0.0;
 }
 
 // back-substitution, model cost change and candidate point: LPP lanes per point (see point_pass_kernel).  The candidate's
 // cost is not evaluated here: cam_pass<CAND> behind this launch evaluates the candidate's residuals with their Jacobians, and
 // its cost decides the step.  (A second sweep here used to evaluate the same residuals for the cost alone, and after an
 // accepted step cam_pass<LIN> evaluated them once more; c3: this launch 0.101 -> 0.079 ms without that sweep.)
-// FYM = 1 (round 4, OPT-IN: vgg_ba_set_step_from_factors / VGG_STEP_FACTORS; measured SLOWER, see below): the tile blocks
-// are 6 x 6 and the segment buffer holds the compressed Schur factors N = Jw^T (E G), 2 a of every observation
-// (point_pass_kernel, CY).  Then E^T F dy -- all this kernel needs of the Jacobians -- is there already:
-// F_pose dy = Jw (dy_t - 2 a x dy_w), so G^T sum E^T F dy = sum N^T (dy_t - 2 a x dy_w): one 96-byte record and ~25
-// multiply-adds per observation instead of a second evaluation of the projection and its Jacobians (~150 FP64 operations);
-// the shared intrinsics' share is Ms (dy_a / scale) per point, and the part of the model cost change that only depends on
-// the camera step comes from the cameras' U, g (cam_update_kernel).  Same step to rounding
-// (tests/test_gpu_ba.py::test_ba_step_from_factors_matches_evaluation).  c3, same box
-// (profiles/r04_ab_step_from_factors_c3.jsonl): 0.143 ms re-evaluating (210 VGPRs, 2 wavefronts / SIMD, FP64 issue bound),
-// 0.170 ms from the factors (160 VGPRs, 3 wavefronts / SIMD): a point's records lie in as many segments as it has
-// observations, each 96-byte record touches 1.5 cache lines on average -- 5 M x 192 B = 0.96 GB of line traffic in 0.17 ms
-// is the memory system's limit for this access pattern.  FYM = 2, every other sweep of a lane from the factors so that
-// both pipes have work: 0.147 ms -- no better than re-evaluating.  So the default stays 0.
-template <int KD, bool LDSCAM, int LPP, bool LONGT = false, int FYM = 0>
-__global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void point_step_kernel(DevProblem pb, Ws w) {
-  constexpr bool FY = FYM == 1;                  // every observation from its factor
-  constexpr bool HY = FYM == 2;                  // (measurement only) odd sweeps from the factors, even sweeps re-evaluated
+template <int KD, bool LDSCAM, int LPP, bool LONGT = false>
+__global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem pb, Ws w) {
   constexpr int BD = 6 + KD;
   __shared__ double red[4][3];
-  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy_pose[6C] flags[C]   (FY: dy only)
+  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy_pose[6C] flags[C]
   if (w.ctl->done) return;
   const Dims& d = pb.d;
   constexpr int PPW = 64 / LPP;
@@ -2362,18 +2016,16 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
   const int nw = gridDim.x * 4 * PPW;
   double s_mcc = 0, s_step = 0, s_xn = 0;
   const double* lq = cam_cache;                  // rotation matrices [9C]
-  const double* lt = lq + (FY ? 0 : 9 * d.C);
-  const double* ldy = lt + (FY ? 0 : 3 * d.C);
+  const double* lt = lq + 9 * d.C;
+  const double* ldy = lt + 3 * d.C;
   const double* lfl = ldy + 6 * d.C;
   if (LDSCAM) {
     double* cc = cam_cache;
-    if (!FY) {
-      for (int i = threadIdx.x; i < d.C; i += 256) {
-        quat_to_R(pb.cam_q + 4 * i, cc + 9 * i);
-        cc[18 * d.C + i] = pb.cam_const ? (double)pb.cam_const[i] : 0.0;
-      }
-      for (int i = threadIdx.x; i < 3 * d.C; i += 256) cc[9 * d.C + i] = pb.cam_t[i];
+    for (int i = threadIdx.x; i < d.C; i += 256) {
+      quat_to_R(pb.cam_q + 4 * i, cc + 9 * i);
+      cc[18 * d.C + i] = pb.cam_const ? (double)pb.cam_const[i] : 0.0;
     }
+    for (int i = threadIdx.x; i < 3 * d.C; i += 256) cc[9 * d.C + i] = pb.cam_t[i];
     for (int i = threadIdx.x; i < 6 * d.C; i += 256) cc[(ldy - cam_cache) + i] = w.dy[i];
     __syncthreads();
   }
@@ -2395,7 +2047,7 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
     n_o0 = pb.row_ptr[p]; n_o1 = pb.row_ptr[p + 1];
     n_X0 = pb.pts[3 * p]; n_X1 = pb.pts[3 * p + 1]; n_X2 = pb.pts[3 * p + 2];
     n_ptc = pb.pt_const ? (int)pb.pt_const[p] : 0;
-    n_pf.template load<(FYM != 0)>(pb.obs_cam, pb.obs_uv, pb.obs_slot, n_o0, n_o1, LPP, sl);
+    n_pf.template load<false>(pb.obs_cam, pb.obs_uv, pb.obs_slot, n_o0, n_o1, LPP, sl);
     if (p + nw < d.P) {
       const int pm = p + nw;
       m_o0 = pb.row_ptr[pm]; m_o1 = pb.row_ptr[pm + 1];
@@ -2411,7 +2063,7 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
     {
       // stage 1 -> current of the next iteration: observations of point p + nw (its bounds arrived an iteration ago)
       n_o0 = m_o0; n_o1 = m_o1; n_X0 = m_X0; n_X1 = m_X1; n_X2 = m_X2; n_ptc = m_ptc;
-      if (p + nw < d.P) n_pf.template load<(FYM != 0)>(pb.obs_cam, pb.obs_uv, pb.obs_slot, n_o0, n_o1, LPP, sl);
+      if (p + nw < d.P) n_pf.template load<false>(pb.obs_cam, pb.obs_uv, pb.obs_slot, n_o0, n_o1, LPP, sl);
       // stage 2: bounds / coordinates of point p + 2 nw
       const int pm = p + 2 * nw;
       if (pm < d.P) {
@@ -2433,21 +2085,6 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
     // and with (V + D^2) ys = g - t3 and (V + D^2)^-1 = G G^T (point_pass):  ys^T (g - t3) = |G^-1 ys|^2 =: |z|^2, so
     //   = sum [F dy . r - |F dy|^2 / 2]  +  |z|^2 / 2  +  ys^T D^2 ys / 2.
     // The bracket is accumulated in the sweep.
-    double uf[3] = {0, 0, 0};                      // G^T sum E^T F_pose dy over the observations taken from their factors
-    auto from_factor = [&](int pass, int o) __attribute__((always_inline)) {
-      const int c = f_pf.cam(pass, pb.obs_cam, o);
-      const int slot = f_pf.slot(pass, pb.obs_slot, o);
-      const double2* y = reinterpret_cast<const double2*>(w.Y + (size_t)slot * kYc);
-      const double2 n01 = y[0], n23 = y[1], n45 = y[2], n67 = y[3], n8a = y[4], a12 = y[5];
-      const double* dyc = LDSCAM ? ldy + 6 * c : w.dy + 6 * c;
-      const double a0 = n8a.y, a1 = a12.x, a2 = a12.y;                 // 2 a
-      const double v0 = dyc[3] - (a1 * dyc[2] - a2 * dyc[1]);
-      const double v1 = dyc[4] - (a2 * dyc[0] - a0 * dyc[2]);
-      const double v2 = dyc[5] - (a0 * dyc[1] - a1 * dyc[0]);
-      uf[0] += n01.x * v0 + n23.y * v1 + n67.x * v2;                   // N row-major: N[i][m] = rec[3 i + m]
-      uf[1] += n01.y * v0 + n45.x * v1 + n67.y * v2;
-      uf[2] += n23.x * v0 + n45.y * v1 + n8a.x * v2;
-    };
     auto evaluated = [&](int pass, int o) __attribute__((always_inline)) {
       const int c = f_pf.cam(pass, pb.obs_cam, o);
       const float2 uv = f_pf.uv(pass, pb.obs_uv, o);
@@ -2462,37 +2099,20 @@ __global__ __launch_bounds__(256, FYM == 1 ? VGG_PS_OCC_FY : VGG_PS_OCC) void po
       double fy0 = 0, fy1 = 0;
 #pragma unroll
       for (int k = 0; k < 6; ++k) { const double v = LDSCAM ? ldy[6 * c + k] : w.dy[6 * c + k]; fy0 += F[k] * v; fy1 += F[BD + k] * v; }
-      if (!HY) {                                   // (HY: the intrinsics' share comes from Ms for every observation)
 #pragma unroll
-        for (int k = 0; k < KD; ++k) { const double v = w.dy[6 * d.C + KD * a + k]; fy0 += F[6 + k] * v; fy1 += F[BD + 6 + k] * v; }
-      }
+      for (int k = 0; k < KD; ++k) { const double v = w.dy[6 * d.C + KD * a + k]; fy0 += F[6 + k] * v; fy1 += F[BD + 6 + k] * v; }
       t3[0] += E[0] * fy0 + E[3] * fy1; t3[1] += E[1] * fy0 + E[4] * fy1; t3[2] += E[2] * fy0 + E[5] * fy1;
-      if (!HY) s_mcc += fy0 * (r[0] - 0.5 * fy0) + fy1 * (r[1] - 0.5 * fy1);      // (HY / FY: from the cameras' U, g)
+      s_mcc += fy0 * (r[0] - 0.5 * fy0) + fy1 * (r[1] - 0.5 * fy1);
     };
-    for (int o = o0 + sl; o < o1; o += LPP) {
-      const int pass = (o - o0) / LPP;
-      if (FY || (HY && (pass & 1))) from_factor(pass, o);
-      else evaluated(pass, o);
-    }
+    for (int o = o0 + sl; o < o1; o += LPP) evaluated((o - o0) / LPP, o);
 #pragma unroll
     for (int i = 0; i < 3; ++i) t3[i] = group_sum<LPP>(t3[i]);
-    // ys = hs - G (G^T t3 + uf)   (the shared intrinsics add Ms (dy_a / scale_a) when factors are used)
-    double u0 = 0, u1 = 0, u2 = 0;
-    if (!FY) { u0 = G00 * t3[0]; u1 = G01 * t3[0] + G11 * t3[1]; u2 = G02 * t3[0] + G12 * t3[1] + G22 * t3[2]; }
-    if (FYM != 0) { u0 += group_sum<LPP>(uf[0]); u1 += group_sum<LPP>(uf[1]); u2 += group_sum<LPP>(uf[2]); }
+    // ys = hs - G G^T t3
+    const double u0 = G00 * t3[0], u1 = G01 * t3[0] + G11 * t3[1], u2 = G02 * t3[0] + G12 * t3[1] + G22 * t3[2];
     double ys[3];
     ys[0] = hs0 - (G00 * u0 + G01 * u1 + G02 * u2);
     ys[1] = hs1 - (G11 * u1 + G12 * u2);
     ys[2] = hs2 - (G22 * u2);
-    if constexpr (FYM != 0 && KD > 0) {
-      const double* Msp = w.Ms + (size_t)p * 3 * KD;
-#pragma unroll
-      for (int m = 0; m < KD; ++m) {
-        const int j = 6 * d.C + m;
-        const double ds = w.active[j] ? w.rhs[j] : 0.0;
-        ys[0] -= Msp[3 * m] * ds; ys[1] -= Msp[3 * m + 1] * ds; ys[2] -= Msp[3 * m + 2] * ds;
-      }
-    }
     if (sl == 0) {
       w.cand_pts[3 * (size_t)p] = X[0] - ys[0]; w.cand_pts[3 * (size_t)p + 1] = X[1] - ys[1]; w.cand_pts[3 * (size_t)p + 2] = X[2] - ys[2];
       s_step += ys[0] * ys[0] + ys[1] * ys[1] + ys[2] * ys[2];
@@ -2779,7 +2399,7 @@ static size_t split_count_a(const Dims& d) {
 
 // workgroups per camera of the camera passes: ~1024 workgroups in total for a large problem (c3: 19 observations per
 // thread; 2048 workgroups cost 0.117 + 0.131 ms, 1024: 0.099 + 0.128, 512: 0.105 + 0.146), at least ~2048 observations per
-// workgroup for a small one (c2: 512 workgroups 0.025 + 0.019 ms, 1024: 0.038 + 0.026).  VGG_CAM_WGS overrides the total.
+// workgroup for a small one (c2: 512 workgroups 0.025 + 0.019 ms, 1024: 0.038 + 0.026).  vgg_ba_tuning overrides the total.
 static inline int cam_split_for(int C, int O) {
   const int target = g_tuning.cam_wgs > 0 ? g_tuning.cam_wgs : min(1024, max(256, O / 2048));
   const int s = target / (C > 0 ? C : 1);
@@ -2808,18 +2428,8 @@ static void launch_schur_batch(const Launch& L, int batch, hipStream_t st, doubl
     ProfScope ps(kProfSchurTile, st);
     schur_tile_merged_kernel<BD><<<c1 - c0, 256, 0, st>>>(L.w, L.chunk_desc, L.entries, c0, L.num_segments);
   } else if (cm > c0 && which != 2) {
-    if (BD == 6 && L.w.tile_dma) {                 // round-6 A/B: LDS-DMA staging from the expanded segment image
-      {
-        ProfScope ps(kProfCamRhs, st);              // (the slot of cam_pass<RHS>, which tile_rhs leaves empty: the expansion, timed apart)
-        expand_segments_kernel<<<div_up((L.num_segments + 1) * kGroup, 256), 256, 0, st>>>(L.w, L.num_segments);
-      }
-      ProfScope ps(kProfSchurTile, st);
-      if (L.w.tile_dma == 2) schur_tile_dma_kernel<2><<<cm - c0, 256, 0, st>>>(L.w, L.chunk_desc, L.entries, c0, L.num_segments);
-      else schur_tile_dma_kernel<1><<<cm - c0, 256, 0, st>>>(L.w, L.chunk_desc, L.entries, c0, L.num_segments);
-    } else {
-      ProfScope ps(kProfSchurTile, st);
-      schur_tile_kernel<BD, false><<<cm - c0, 256, 0, st>>>(L.w, L.chunk_desc, L.entries, c0, L.num_segments);
-    }
+    ProfScope ps(kProfSchurTile, st);
+    schur_tile_kernel<BD, false><<<cm - c0, 256, 0, st>>>(L.w, L.chunk_desc, L.entries, c0, L.num_segments);
   }
   if (!L.merged_tile_launch && c1 > cm && which != 1) {
     ProfScope ps(kProfSchurTileDiag, st);
@@ -2831,13 +2441,12 @@ static void launch_schur_batch(const Launch& L, int batch, hipStream_t st, doubl
 }
 
 template <int KD>
-static void launch_schur_batches(const Launch& L, int b0, int b1, hipStream_t st, double* dst, hipEvent_t* done_events,
-                                 int32_t* done_flags = nullptr, int which = 0) {
+static void launch_schur_batches(const Launch& L, int b0, int b1, hipStream_t st, double* dst, int32_t* done_flags = nullptr,
+                                 int which = 0) {
   for (int b = b0; b < b1; ++b) {
     if (L.d.shared || KD == 0) launch_schur_batch<6>(L, b, st, dst, which);
     else launch_schur_batch<6 + KD>(L, b, st, dst, which);
-    if (done_events) (void)hipEventRecord(done_events[b], st);
-    if (done_flags) dataflow_signal(done_flags + b, st);    // (for the single-launch factorisation, which waits on the device)
+    if (done_flags) dataflow_signal(done_flags + b, st);    // (the single-launch factorisation waits on the device)
   }
 }
 
@@ -2847,7 +2456,7 @@ static void launch_schur_batches(const Launch& L, int b0, int b1, hipStream_t st
 struct OverlapCtx {
   int chol_cus = 0;
   hipStream_t st_chol = nullptr, st_rest = nullptr;
-  hipEvent_t ready = nullptr, chol_done = nullptr, batch_done[8] = {};
+  hipEvent_t ready = nullptr, chol_done = nullptr;
 };
 static OverlapCtx* overlap_ctx(const Launch& L) {
   static OverlapCtx ctx[16];
@@ -2871,7 +2480,6 @@ static OverlapCtx* overlap_ctx(const Launch& L) {
             hipExtStreamCreateWithCUMask(&c.st_rest, words, mask_rest) == hipSuccess &&
             hipEventCreateWithFlags(&c.ready, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c.chol_done, hipEventDisableTiming) == hipSuccess;
-  for (int i = 0; ok && i < 8; ++i) ok = hipEventCreateWithFlags(&c.batch_done[i], hipEventDisableTiming) == hipSuccess;
   if (!ok) { (void)hipGetLastError(); failed[dev] = true; return nullptr; }
   c.chol_cus = cus;
   return &c;
@@ -2883,7 +2491,7 @@ template <int KD>
 static void phase_schur(const Launch& L, int which = 0) {
   const Dims& d = L.d;
   if (which == 2) {
-    if (L.num_chunks > 0) launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S, nullptr, nullptr, 2);
+    if (L.num_chunks > 0) launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S, nullptr, 2);
     assemble_kernel<KD><<<d.C + 1, 64, 0, L.st>>>(L.dp, L.w, L.tile_desc, L.num_tiles, L.wgB);
     return;
   }
@@ -2925,16 +2533,16 @@ static void phase_schur(const Launch& L, int which = 0) {
   }
   // (the reduced system was zeroed by cam_pass_kernel<KD, 1>: no fill launch)
   if (which == 1) {
-    if (L.num_chunks > 0) launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S, nullptr, nullptr, 1);
+    if (L.num_chunks > 0) launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S, nullptr, 1);
     return;
   }
   if (L.num_chunks > 0) {
     if (overlap_ctx(L)) {
       // only the first batch here; the others are enqueued by phase_step beside the factorisation and land in S2
       (void)hipMemsetAsync(L.w.S2, 0, sizeof(double) * (size_t)d.n_red * d.n_red, L.st);
-      launch_schur_batches<KD>(L, 0, 1, L.st, L.w.S, nullptr);
+      launch_schur_batches<KD>(L, 0, 1, L.st, L.w.S);
     } else {
-      launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S, nullptr);
+      launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S);
     }
   }
   assemble_kernel<KD><<<d.C + 1, 64, 0, L.st>>>(L.dp, L.w, L.tile_desc, L.num_tiles, L.wgB);
@@ -2945,34 +2553,31 @@ static int phase_step(const Launch& L) {
   const Dims& d = L.d;
   size_t chol_flag_count = 0;
   int32_t* chol_flags = cholesky_dataflow_flags(L.w.chol_inv, d.n_red, &chol_flag_count);
-  begin_iteration_kernel<<<1, 256, 0, L.st>>>(L.w, L.opt, d.n_red, chol_flags, chol_flags ? (int)chol_flag_count : 0);
+  begin_iteration_kernel<<<1, 256, 0, L.st>>>(L.w, L.opt, d.n_red, chol_flags, (int)chol_flag_count);
   int rc;
   if (OverlapCtx* oc = overlap_ctx(L)) {
     (void)hipMemsetAsync(L.w.batch_flags, 0, 64, L.st);
     (void)hipEventRecord(oc->ready, L.st);
     (void)hipStreamWaitEvent(oc->st_rest, oc->ready, 0);
     (void)hipStreamWaitEvent(oc->st_chol, oc->ready, 0);
-    launch_schur_batches<KD>(L, 1, L.num_batches, oc->st_rest, L.w.S2, oc->batch_done, L.w.batch_flags);
+    launch_schur_batches<KD>(L, 1, L.num_batches, oc->st_rest, L.w.S2, L.w.batch_flags);
     CholOverlap ov;
     ov.dev_flags = L.w.batch_flags + 1;            // flag of wait k = batch k + 1
     ov.S2 = L.w.S2;
     ov.first_col = 6 * kGroup * L.batches[6 * 1 + 5];
     ov.num_waits = L.num_batches - 1;
-    for (int b = 1; b < L.num_batches; ++b) {
-      ov.wait_col[b - 1] = 6 * kGroup * L.batches[6 * b + 5];
-      ov.wait_ev[b - 1] = oc->batch_done[b];
-    }
+    for (int b = 1; b < L.num_batches; ++b) ov.wait_col[b - 1] = 6 * kGroup * L.batches[6 * b + 5];
     {
       ProfScope ps(kProfCholesky, oc->st_chol);
       rc = cholesky_solve_enqueue(L.w.S, L.w.rhs, d.n_red, L.w.chol_inv, &L.w.ctl->linear_fail, &L.w.ctl->done, oc->st_chol, &ov,
-                                  L.chol_split_a, L.chol_split_b, L.chol_first_blk, chol_flags != nullptr);
+                                  L.chol_split_a, L.chol_split_b, L.chol_first_blk, true);
     }
     (void)hipEventRecord(oc->chol_done, oc->st_chol);
     (void)hipStreamWaitEvent(L.st, oc->chol_done, 0);
   } else {
     ProfScope ps(kProfCholesky, L.st);
     rc = cholesky_solve_enqueue(L.w.S, L.w.rhs, d.n_red, L.w.chol_inv, &L.w.ctl->linear_fail, &L.w.ctl->done, L.st, nullptr,
-                                L.chol_split_a, L.chol_split_b, L.chol_first_blk, chol_flags != nullptr);
+                                L.chol_split_a, L.chol_split_b, L.chol_first_blk, true);
   }
   if (rc != VGG_OK) return rc;
   cam_update_kernel<KD><<<div_up(d.C + 1, 64), 64, 0, L.st>>>(L.dp, L.w);
@@ -2982,18 +2587,11 @@ static int phase_step(const Launch& L) {
     auto launch = [&](auto lpp) {
       constexpr int LPP = decltype(lpp)::value;
       const bool longt = long_tracks(LPP, L.d.P, L.d.O);
-      auto go = [&](auto fy) {
-        constexpr int FY = decltype(fy)::value;
-        const size_t lds = FY == 1 ? sizeof(double) * 6 * (size_t)d.C : cam_lds;
-        if (longt && LPP <= 32) {
-          if (lds <= 64 * 1024) point_step_kernel<KD, true, LPP, (LPP <= 32), FY><<<L.wgB, 256, lds, L.st>>>(L.dp, L.w);
-          else point_step_kernel<KD, false, LPP, (LPP <= 32), FY><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
-        } else if (lds <= 64 * 1024) point_step_kernel<KD, true, LPP, false, FY><<<L.wgB, 256, lds, L.st>>>(L.dp, L.w);
-        else point_step_kernel<KD, false, LPP, false, FY><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
-      };
-      if (L.w.step_from_factors == 1) go(std::integral_constant<int, 1>{});
-      else if (L.w.step_from_factors == 2) go(std::integral_constant<int, 2>{});
-      else go(std::integral_constant<int, 0>{});
+      if (longt && LPP <= 32) {
+        if (cam_lds <= 64 * 1024) point_step_kernel<KD, true, LPP, (LPP <= 32)><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w);
+        else point_step_kernel<KD, false, LPP, (LPP <= 32)><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
+      } else if (cam_lds <= 64 * 1024) point_step_kernel<KD, true, LPP><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w);
+      else point_step_kernel<KD, false, LPP><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
     };
     if (L.lpp == 8) launch(std::integral_constant<int, 8>{});
     else if (L.lpp == 16) launch(std::integral_constant<int, 16>{});
@@ -3076,8 +2674,6 @@ static int make_launch(const vgg_ba_problem* pb, const vgg_ba_options* opt, void
   //  camera pass, 2 = everywhere)
   L->w.tile_rhs = (g_tuning.tile_rhs && (L->d.shared || L->d.kd == 0 || g_tuning.tile_rhs >= 2) && pb->num_chunks > 0 &&
                    pb->num_tile_batches == 1) ? 1 : 0;
-  L->w.step_from_factors = (L->d.shared || L->d.kd == 0) ? g_tuning.step_factors : 0;      // (compressed factors in the segment buffer)
-  L->w.tile_dma = (L->w.Yx && !pb->merged_tile_launch && pb->num_tile_batches == 1) ? g_tuning.tile_dma : 0;
   L->cam_q = pb->cam_q; L->cam_t = pb->cam_t; L->intr = pb->intr; L->pts = pb->pts;
   return VGG_OK;
 }
@@ -3150,23 +2746,12 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
   if (!(lanes_per_point == 0 || lanes_per_point == 8 || lanes_per_point == 16 || lanes_per_point == 32 || lanes_per_point == 64))
     return VGG_ERR_INVALID_ARGUMENT;
   vgg::g_tuning = vgg::Tuning{lanes_per_point, long_tracks < 0 ? -1 : (long_tracks ? 1 : 0), cam_workgroups > 0 ? cam_workgroups : 0,
-                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs, vgg::g_tuning.step_factors,
-                              vgg::g_tuning.tile_dma};
+                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs};
   return VGG_OK;
 }
 
 int vgg_ba_set_tile_rhs(int enable) {
   vgg::g_tuning.tile_rhs = (enable >= 0 && enable <= 2) ? enable : 1;
-  return VGG_OK;
-}
-
-int vgg_ba_set_tile_dma(int mode) {
-  vgg::g_tuning.tile_dma = (mode >= 0 && mode <= 2) ? mode : 0;
-  return VGG_OK;
-}
-
-int vgg_ba_set_step_from_factors(int enable) {
-  vgg::g_tuning.step_factors = (enable == 1 || enable == 2) ? enable : 0;
   return VGG_OK;
 }
 

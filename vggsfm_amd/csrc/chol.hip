@@ -2,10 +2,10 @@
 //
 // In the reference this is the DENSE_SCHUR / SPARSE_SCHUR factorisation inside Ceres, reached through
 // pycolmap.bundle_adjustment (vggsfm/utils/triangulation.py:213,1050,1142).  Two paths:
-//   * n >= 128 with the right-hand side stored behind the matrix (what bundle adjustment passes): ONE launch, a
+//   * the right-hand side stored behind the matrix (what bundle adjustment passes), every n: ONE launch, a
 //     workgroup per 64 x 64 tile, left-looking, tiles handed over through per-tile flags -- chol_dataflow_kernel and
 //     chol_backward_dataflow_kernel in the second half of this file;
-//   * otherwise (and with VGG_CHOL_LEGACY=1): the multi-launch form described next -- right-looking blocked
+//   * a separate right-hand side: the multi-launch form described next -- right-looking blocked
 //     Cholesky, two launches per block column of NB columns:
 //   panel  : every workgroup re-factors the NB x NB diagonal block in LDS (outer-product form, ONE barrier per
 //            column, reciprocal instead of divide), then solves the panel rows below by forward
@@ -17,11 +17,8 @@
 // a ~250 ns pivot step per column.  The kernels are templates on NB; NB = 64 (half the launches) was measured
 // and lost: its panel kernel takes 84 us against 2 x 18 us (the 64 x 64 factor and the 2016 broadcast LDS reads
 // of the substitution are LDS-issue bound), so NB = 32 is what runs.
-// The right-hand side is stored as row n of the (n+1) x n array, so the factorisation performs the
-// forward substitution on the way; the backward substitution is a sequence of NB x NB mat-vecs with T_k.
+// The forward substitution is a launch of its own; the backward substitution is a sequence of NB x NB mat-vecs with T_k.
 // Only the lower triangle (row-major, ld = n) is read or written.
-#include <cstdlib>
-
 #include "common.hpp"
 
 namespace vgg {
@@ -39,57 +36,14 @@ __device__ __forceinline__ double fast_rcp(double x) {
   return r;
 }
 
-// The 256 threads of a workgroup factor the NB x NB block D (LDS, ld = NB + 1, rows >= nb padded with the
-// identity) in place.  Outer-product form WITHOUT normalising inside the loop (a_ic -= a_ij a_cj / d_j), so
-// a step needs a single barrier: the column it reads was finalised by the previous step, the elements it
-// writes are disjoint from it.  Columns are scaled by 1/sqrt(d_j) at the end; rdiag[j] = 1 / L_jj.
-template <int NB>
-__device__ __forceinline__ void factor_diag_lds(double* D, double* rdiag, int32_t* fail_flag) {
-  constexpr int LD = NB + 1, STRIDE = 256 / NB, CNT = NB / STRIDE;
-  const int tid = threadIdx.x;
-  const int c = tid % NB, i0 = tid / NB;        // thread owns elements (i0 + STRIDE m, c), m = 0..CNT-1
-  bool bad = false;
-  for (int j = 0; j < NB - 1; ++j) {
-    __syncthreads();
-    const double dj = D[j * LD + j];
-    if (!(dj > 0.0) || !(dj < 1.7976931348623157e308)) bad = true;
-    const double inv = fast_rcp<1>((dj > 0.0) ? dj : 1.0);
-    if (c > j) {
-      const double lcj = D[c * LD + j] * inv;
-#pragma unroll
-      for (int m = 0; m < CNT; ++m) {
-        const int i = i0 + STRIDE * m;
-        if (i >= c) D[i * LD + c] -= D[i * LD + j] * lcj;
-      }
-    }
-  }
-  __syncthreads();
-  {
-    const double dl = D[(NB - 1) * LD + NB - 1];
-    if (!(dl > 0.0) || !(dl < 1.7976931348623157e308)) bad = true;
-  }
-  // scale column c by 1/sqrt(d_c)
-  const double dc = D[c * LD + c];
-  const double sd = sqrt((dc > 0.0) ? dc : 1.0);
-  const double rs = 1.0 / sd;
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < CNT; ++m) {
-    const int i = i0 + STRIDE * m;
-    if (i > c) D[i * LD + c] *= rs;
-    else if (i == c) { D[i * LD + c] = sd; rdiag[c] = rs; }
-  }
-  if (bad && tid == 0 && fail_flag) *fail_flag = 1;
-  __syncthreads();
-}
-
-// The same factorisation FOUR pivot columns per synchronisation.  The pivot chain of the column-at-a-time version costs
-// a barrier + an LDS round trip + a reciprocal per column (~280 ns); here every thread factors the 4 x 4 pivot block
+// The 256 threads of a workgroup factor the NB x NB block D (LDS, ld = NB + 1, rows >= nb padded with the identity) in
+// place: outer-product form WITHOUT normalising inside the loop (a_ic -= a_ij (a_cj / d_j), j ascending), columns scaled by
+// 1 / sqrt(d_c) at the end; rdiag[j] = 1 / L_jj.  FOUR pivot columns per synchronisation (a column at a time costs a barrier
+// + an LDS round trip + a reciprocal per column, ~280 ns): every thread factors the 4 x 4 pivot block
 // redundantly in registers (broadcast LDS reads, four dependent reciprocals), one thread per row pushes its 4 panel
 // entries through it (u_r0..u_r3, the unnormalised multipliers, and their products with the pivot reciprocals) into a
 // small LDS panel, and the trailing update of an element is one rank-4 step: three barriers per four columns.
-// Arithmetic is that of factor_diag_lds, operation for operation (a_ic -= a_ij (a_cj / d_j), j ascending, columns scaled
-// by 1 / sqrt(d_c) at the end): the factor is bit-identical.
+// The arithmetic is that of the column-at-a-time form, operation for operation: the factor is bit-identical to it.
 // WITH_T: the rows of the identity in Tl (LDS, ld = NB + 1) receive the same column operations, so that Tl ends up as
 // L^-T (what the panel product and the backward substitution need) without a second, dependent pass.
 // scratch: 2 * (WITH_T ? 2 : 1) * NB * 4 doubles of LDS.
@@ -197,232 +151,11 @@ __device__ __forceinline__ void factor_diag_lds4(double* D, double* Tl, double* 
   __syncthreads();
 }
 
-// factor_diag_lds4 with LOOK-AHEAD: the pivot chain of a step (four dependent reciprocals, ~700 cycles that every thread
-// used to repeat before anything else could start) is computed for step j + 1 by the LAST wavefront while the other three
-// apply the trailing update of step j.  That wavefront first brings the next 4 x 4 pivot block up to date itself (the same
-// rank-4 expressions, in the same order, that the trailing update would have applied -- the factor stays bit-identical),
-// runs the chain and leaves the 13 numbers every thread needs (reciprocals, multipliers, eliminated block entries) in a
-// small LDS record.  Per step: barrier, read the record, panel rows, barrier, {chain | update}.
-// MEASURED SLOWER (opt-in, -DVGG_CHOL_LOOKAHEAD): c3 factorisation 0.505 -> 0.548 ms, c2 0.208 -> 0.221, a c4 shard 1.36 ->
-// 1.46.  The trailing update it takes off the critical path is the cheap part of a step; the chain + the panel rows are
-// the step, and the record adds LDS round trips (record write -> barrier -> read; U / V / D reads of the chain wavefront)
-// to exactly that path.  Same factor (tests/test_gpu_ba.py::test_cholesky_* pass with it).
-// scratch: 2 * ROWS * 4 doubles (U, V) + 16 (pivot record).
-template <int NB, bool WITH_T, int LD = NB + 1>
-__device__ __forceinline__ void factor_diag_lds4_la(double* D, double* Tl, double* rdiag, double* scratch, int32_t* fail_flag) {
-  static_assert(NB % 4 == 0 && NB <= 64, "block of 4-column steps");
-  constexpr int ROWS = WITH_T ? 2 * NB : NB;
-  constexpr int UT = 192;                          // threads of the trailing update (wavefronts 0..2)
-  constexpr int STRIDE = UT / NB, CNT = (NB + STRIDE - 1) / STRIDE;
-  static_assert(UT % NB == 0 && ROWS <= UT, "update layout");
-  double* U = scratch;                             // [ROWS][4] unnormalised panel entries u_rt
-  double* V = scratch + ROWS * 4;                  // [ROWS][4] u_rt / d_t
-  double* PR = scratch + 2 * ROWS * 4;             // pivot record: r0..r3, m10 m20 m30 m21 m31 m32, d1 u21 d2 u31 u32 d3 (16)
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = tid % NB, i0 = tid / NB;           // (update threads only: tid < UT)
-  bool bad = false;
-  constexpr double HUGE_ = 1.7976931348623157e308;
-  if (WITH_T) {
-    for (int e = tid; e < NB * NB; e += 256) Tl[(e / NB) * LD + (e % NB)] = (e / NB == e % NB) ? 1.0 : 0.0;
-  }
-  // pivot chain of the 4 x 4 block (values given) -> record; every lane of the calling wavefront computes the same
-  auto chain = [&](double d0, double u10, double p11, double u20, double p21, double p22, double u30, double p31, double p32, double p33) {
-    const double r0 = fast_rcp<1>((d0 > 0.0) ? d0 : 1.0);
-    const double m10 = u10 * r0, m20 = u20 * r0, m30 = u30 * r0;
-    const double d1 = p11 - u10 * m10;
-    const double u21 = p21 - u20 * m10, u31 = p31 - u30 * m10;
-    const double r1 = fast_rcp<1>((d1 > 0.0) ? d1 : 1.0);
-    const double m21 = u21 * r1, m31 = u31 * r1;
-    const double d2 = (p22 - u20 * m20) - u21 * m21;
-    const double u32 = (p32 - u30 * m20) - u31 * m21;
-    const double r2 = fast_rcp<1>((d2 > 0.0) ? d2 : 1.0);
-    const double m32 = u32 * r2;
-    const double d3 = ((p33 - u30 * m30) - u31 * m31) - u32 * m32;
-    const double r3 = fast_rcp<1>((d3 > 0.0) ? d3 : 1.0);
-    if (!(d0 > 0.0) || !(d0 < HUGE_) || !(d1 > 0.0) || !(d1 < HUGE_) || !(d2 > 0.0) || !(d2 < HUGE_) || !(d3 > 0.0) || !(d3 < HUGE_))
-      bad = true;
-    if ((tid & 63) == 0) {
-      PR[0] = r0; PR[1] = r1; PR[2] = r2; PR[3] = r3;
-      PR[4] = m10; PR[5] = m20; PR[6] = m30; PR[7] = m21; PR[8] = m31; PR[9] = m32;
-      PR[10] = d1; PR[11] = u21; PR[12] = d2; PR[13] = u31; PR[14] = u32; PR[15] = d3;
-    }
-  };
-  __syncthreads();
-  if (wave == 3) {                                 // record of step 0: the block as it stands
-    const double* P = D;
-    chain(P[0], P[LD], P[LD + 1], P[2 * LD], P[2 * LD + 1], P[2 * LD + 2], P[3 * LD], P[3 * LD + 1], P[3 * LD + 2], P[3 * LD + 3]);
-  }
-  for (int j0 = 0; j0 < NB; j0 += 4) {
-    __syncthreads();                               // record of this step written; all earlier updates applied
-    const double r0 = PR[0], r1 = PR[1], r2 = PR[2], r3 = PR[3];
-    const double m10 = PR[4], m20 = PR[5], m30 = PR[6], m21 = PR[7], m31 = PR[8], m32 = PR[9];
-    const double d1 = PR[10], u21 = PR[11], d2 = PR[12], u31 = PR[13], u32 = PR[14], d3 = PR[15];
-    // one thread per row: the row's four panel entries through the pivot block
-    if (tid < ROWS) {
-      const bool trow = WITH_T && tid >= NB;
-      const int r = trow ? tid - NB : tid;
-      const double* X = (trow ? Tl : D) + r * LD + j0;
-      const bool live = trow ? (r < j0 + 4) : (r >= j0 + 4);
-      double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;
-      if (live) {
-        x0 = X[0];
-        x1 = X[1] - x0 * m10;
-        x2 = (X[2] - x0 * m20) - x1 * m21;
-        x3 = ((X[3] - x0 * m30) - x1 * m31) - x2 * m32;
-      }
-      double* Ur = U + tid * 4;
-      double* Vr = V + tid * 4;
-      Ur[0] = x0; Ur[1] = x1; Ur[2] = x2; Ur[3] = x3;
-      Vr[0] = x0 * r0; Vr[1] = x1 * r1; Vr[2] = x2 * r2; Vr[3] = x3 * r3;
-    }
-    __syncthreads();                               // panel in place; everybody has read the record
-    const int jn = j0 + 4;                         // first column of the NEXT pivot block
-    if (wave == 3) {
-      if (jn < NB) {
-        // next pivot block: apply this step's rank-4 update to its 10 entries (as the trailing update does), store, chain
-        double q[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b = 0; b <= a; ++b) {
-            const double* Ua = U + (jn + a) * 4;
-            const double* Vb = V + (jn + b) * 4;
-            double v = D[(jn + a) * LD + jn + b];
-            v -= Ua[0] * Vb[0]; v -= Ua[1] * Vb[1]; v -= Ua[2] * Vb[2]; v -= Ua[3] * Vb[3];
-            q[a][b] = v;
-          }
-        if ((tid & 63) == 0) {
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b <= a; ++b) D[(jn + a) * LD + jn + b] = q[a][b];
-        }
-        chain(q[0][0], q[1][0], q[1][1], q[2][0], q[2][1], q[2][2], q[3][0], q[3][1], q[3][2], q[3][3]);
-      }
-    } else {
-      // rank-4 trailing update (columns beyond the panel; the next pivot block belongs to the other wavefront)
-      if (c >= jn) {
-        const double v0 = V[c * 4], v1 = V[c * 4 + 1], v2 = V[c * 4 + 2], v3 = V[c * 4 + 3];
-#pragma unroll
-        for (int m = 0; m < CNT; ++m) {
-          const int i = i0 + STRIDE * m;
-          if (i < NB && i >= c && !(i < jn + 4 && c < jn + 4)) {
-            const double* Ui = U + i * 4;
-            double a = D[i * LD + c];
-            a -= Ui[0] * v0; a -= Ui[1] * v1; a -= Ui[2] * v2; a -= Ui[3] * v3;
-            D[i * LD + c] = a;
-          }
-          if (WITH_T && i < NB && i < jn) {
-            const double* Ui = U + (NB + i) * 4;
-            double a = Tl[i * LD + c];
-            a -= Ui[0] * v0; a -= Ui[1] * v1; a -= Ui[2] * v2; a -= Ui[3] * v3;
-            Tl[i * LD + c] = a;
-          }
-        }
-      }
-      // the panel columns themselves: rows below the pivot block get u_rt; the pivot block its own entries
-      if (tid < ROWS) {
-        const bool trow = WITH_T && tid >= NB;
-        const int r = trow ? tid - NB : tid;
-        double* X = (trow ? Tl : D) + r * LD + j0;
-        const double* Ur = U + tid * 4;
-        if (trow ? (r < j0 + 4) : (r >= j0 + 4)) { X[0] = Ur[0]; X[1] = Ur[1]; X[2] = Ur[2]; X[3] = Ur[3]; }
-      }
-      if (tid == 0) {
-        double* Pw = D + j0 * LD + j0;
-        Pw[LD + 1] = d1; Pw[2 * LD + 1] = u21; Pw[2 * LD + 2] = d2; Pw[3 * LD + 1] = u31; Pw[3 * LD + 2] = u32; Pw[3 * LD + 3] = d3;
-      }
-    }
-  }
-  __syncthreads();
-  // scale column c by 1/sqrt(d_c): all 256 threads again
-  constexpr int STRIDE2 = 256 / NB, CNT2 = NB / STRIDE2;
-  const int c2 = tid % NB, i02 = tid / NB;
-  const double dc = D[c2 * LD + c2];
-  const double sd = sqrt((dc > 0.0) ? dc : 1.0);
-  const double rs = 1.0 / sd;
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < CNT2; ++m) {
-    const int i = i02 + STRIDE2 * m;
-    if (i > c2) D[i * LD + c2] *= rs;
-    else if (i == c2) { D[i * LD + c2] = sd; rdiag[c2] = rs; }
-    if (WITH_T && i <= c2) Tl[i * LD + c2] *= rs;
-  }
-  if (bad && (tid & 63) == 0 && fail_flag) *fail_flag = 1;
-  __syncthreads();
-}
-
 // One double of lane `src` (compile-time constant after unrolling) as a wave-uniform value: two v_readlane_b32.
 __device__ __forceinline__ double readlane_f64(double v, int src) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
   return __hiloint2double(hi, lo);
-}
-
-// The same broadcast through the LDS crossbar (ds_bpermute_b32: no LDS memory involved): the value lands in a VECTOR register.
-// v_readlane writes a scalar pair, and an fp64 instruction on gfx9 takes ONE scalar operand -- a step of factor16_mfma spent 14
-// v_mov_b32 on carrying broadcast values back into vector registers (round 6; VGG_F16_BCAST).  `zero` = a vector register
-// holding 0 (the lane address goes into the instruction's offset field).
-__device__ __forceinline__ double bpermute_f64(double v, int src, int zero) {
-  const int lo = __builtin_amdgcn_ds_bpermute(zero + 4 * src, __double2loint(v));
-  const int hi = __builtin_amdgcn_ds_bpermute(zero + 4 * src, __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-
-// The same factorisation by ONE wavefront with the block in registers: lane i < 32 holds row i of the (symmetric) block,
-// no LDS round trip and no barrier per pivot column -- the multipliers of a column are broadcast with v_readlane.
-// Per column j: d_j = lane j's x[j]; m = x[j] / d_j (every lane: lane c now holds the multiplier of column c);
-// x[c] -= x[j] * m_c for c > j.  Arithmetic and order are those of factor_diag_lds (non-normalised outer product,
-// one Newton step on the pivot reciprocal, columns scaled by 1/sqrt(d_c) at the end): the factor is bit-identical.
-// (Opt-in experiment, see FACTOR_DIAG below: it measured no faster than the LDS version.)
-// D: LDS block (ld = NB + 1), lower triangle valid on entry, factor on exit; rdiag[j] = 1 / L_jj.
-// Must be called by all 64 lanes of one wavefront; the caller synchronises the workgroup afterwards.
-template <int NB>
-__device__ __forceinline__ void factor_diag_wave(double* D, double* rdiag, int32_t* fail_flag) {
-  static_assert(NB == 32, "one row per lane, lanes 0..31");
-  constexpr int LD = NB + 1;
-  const int lane = threadIdx.x & 63;
-  const int i = lane & (NB - 1);
-  double x[NB];
-#pragma unroll
-  for (int c = 0; c < NB; ++c) x[c] = D[(c <= i ? i * LD + c : c * LD + i)];      // full symmetric row
-  bool bad = false;
-  double myd = 1.0;
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const double dj = readlane_f64(x[j], j);
-    if (!(dj > 0.0) || !(dj < 1.7976931348623157e308)) bad = true;
-    if (i == j) myd = x[j];
-    if (j < NB - 1) {
-      const double inv = fast_rcp<1>((dj > 0.0) ? dj : 1.0);
-      const double m = x[j] * inv;
-      // all multipliers of the column first (distinct scalar registers), then the FMAs: back-to-back v_readlane pipeline,
-      // whereas readlane -> fma pairs through one scalar pair wait for the scalar write every time
-      double sc[NB];
-#pragma unroll
-      for (int c = j + 1; c < NB; ++c) sc[c] = readlane_f64(m, c);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int c = j + 1; c < NB; ++c) x[c] -= x[j] * sc[c];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // scale column c by 1/sqrt(d_c): lane c knows d_c; broadcast the 32 scales through LDS (rdiag doubles as staging)
-  const double sd = sqrt((myd > 0.0) ? myd : 1.0);
-  const double rs = 1.0 / sd;
-  if (lane < NB) rdiag[lane] = rs;
-  __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the ds_write above is visible to this wave's reads below
-  __builtin_amdgcn_wave_barrier();
-  if (lane < NB) {
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-      if (c < i) D[i * LD + c] = x[c] * rdiag[c];
-      else if (c == i) D[i * LD + c] = sd;
-    }
-  }
-  if (bad && lane == 0 && fail_flag) *fail_flag = 1;
 }
 
 // x <- x L_kk^-T for one row held in registers.  Column-oriented substitution: once x_k is final it is
@@ -439,31 +172,10 @@ __device__ __forceinline__ void substitute_row(double (&x)[NB], const double* D,
   }
 }
 
-// Diagonal-block factorisation used by the panel kernels: the 256-thread LDS version.  -DVGG_CHOL_WAVE_FACTOR selects the
-// single-wavefront register version (wavefront 2 factors, the workgroup waits) -- built and measured in round 2
-// (scripts/ubench/chol_bench, n = 1202): 1.047 ms against 1.057 ms, i.e. no gain: ~1000 v_readlane_b32 per 32 x 32 block
-// cost what the 32 barrier + LDS round trips cost.
-#if defined(VGG_CHOL_COLUMN_FACTOR)
-#define FACTOR_DIAG(Dp, rdp, failp) factor_diag_lds<NB>(Dp, rdp, failp)
-#elif !defined(VGG_CHOL_WAVE_FACTOR)
-#define FACTOR_DIAG(Dp, rdp, failp) factor_diag_lds4<NB, false>(Dp, nullptr, rdp, fscr, failp)
-#else
-#define FACTOR_DIAG(Dp, rdp, failp)                                          \
-  do {                                                                       \
-    __syncthreads();                                                         \
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 2) {             \
-      if constexpr (NB == 32) factor_diag_wave<32>(Dp, rdp, failp);          \
-    }                                                                        \
-    if constexpr (NB != 32) factor_diag_lds<NB>(Dp, rdp, failp);             \
-    __syncthreads();                                                         \
-  } while (0)
-#endif
-
 template <int NB>
 __global__ __launch_bounds__(256) void chol_panel_kernel(double* __restrict__ A, int n, int nrows, int k0,
                                                          int32_t* fail, const int32_t* skip,
-                                                         double* __restrict__ inv_blocks,
-                                                         const double* __restrict__ S2) {
+                                                         double* __restrict__ inv_blocks) {
   constexpr int LD = NB + 1;
   __shared__ double D[NB * LD];
   __shared__ double rdiag[NB];
@@ -480,11 +192,6 @@ __global__ __launch_bounds__(256) void chol_panel_kernel(double* __restrict__ A,
     const double* Arow = A + (size_t)row * n + k0;
 #pragma unroll
     for (int c = 0; c < NB; ++c) x[c] = Arow[c];   // unconditional: all NB loads in flight at once
-    if (S2 && row < n) {                           // lazily added overlapped-batch contributions (see panel2)
-      const double* Srow = S2 + (size_t)row * n + k0;
-#pragma unroll
-      for (int c = 0; c < NB; ++c) x[c] += Srow[c];
-    }
   } else {
 #pragma unroll
     for (int c = 0; c < NB; ++c) x[c] = (extra_wg && c == tid) ? 1.0 : 0.0;
@@ -492,9 +199,9 @@ __global__ __launch_bounds__(256) void chol_panel_kernel(double* __restrict__ A,
   for (int e = tid; e < NB * NB; e += 256) {
     const int i = e / NB, c = e % NB;
     const size_t o = (size_t)(k0 + i) * n + k0 + c;
-    D[i * LD + c] = (i < nb && c <= i) ? A[o] + (S2 ? S2[o] : 0.0) : ((i == c) ? 1.0 : 0.0);
+    D[i * LD + c] = (i < nb && c <= i) ? A[o] : ((i == c) ? 1.0 : 0.0);
   }
-  FACTOR_DIAG(D, rdiag, (blockIdx.x == 0) ? fail : nullptr);
+  factor_diag_lds4<NB, false>(D, nullptr, rdiag, fscr, (blockIdx.x == 0) ? fail : nullptr);
   if (blockIdx.x == 0) {
     for (int e = tid; e < NB * NB; e += 256) {
       const int i = e / NB, c = e % NB;
@@ -532,15 +239,10 @@ __global__ __launch_bounds__(256) void chol_panel_kernel(double* __restrict__ A,
 // + one K = 64 trailing update instead of two of each (every launch has a ~4.5 us floor plus two dependent
 // memory round trips).  Requires k0 + 64 <= n.  Workgroup = 256 threads for the two 32x32 factorisations;
 // wavefront 0 owns 64 panel rows (one per lane, 64 registers), wavefront 1 solves the 32 rows of L21.
-// blockIdx.y selects one of TWO independent panels (k0 or k0_second) of the same launch: when the leading part of the
-// matrix is block diagonal (column sets A and B with A[B rows][A cols] = 0, see cholesky_solve_enqueue) the panels of
-// the two blocks do not depend on each other and their ~40 us pivot chains run side by side.
-__global__ __launch_bounds__(256) void chol_panel2_kernel(double* __restrict__ A, int n, int nrows, int k0_first,
+__global__ __launch_bounds__(256) void chol_panel2_kernel(double* __restrict__ A, int n, int nrows, int k0,
                                                           int32_t* fail, const int32_t* skip,
-                                                          double* __restrict__ inv_blocks,
-                                                          const double* __restrict__ S2, int k0_second) {
+                                                          double* __restrict__ inv_blocks) {
   constexpr int NB = 32, LD = NB + 1;
-  const int k0 = blockIdx.y ? k0_second : k0_first;
   __shared__ double D1[NB * LD], D2[NB * LD], L21[NB * LD];
   __shared__ double rd1[NB], rd2[NB];
   __shared__ double fscr[8 * NB];
@@ -550,27 +252,14 @@ __global__ __launch_bounds__(256) void chol_panel2_kernel(double* __restrict__ A
   const int row = k0 + 2 * NB + blockIdx.x * 64 + lane;
   const bool has_row = !extra_wg && wave == 0 && row < nrows;
   double x[2 * NB];                               // wave 0: the panel row; wave 1 (lanes < 32): row of B21 in x[0..31]
-  // S2 (optional, n x n, same layout): contributions to these 64 columns that were computed while earlier columns
-  // were being factored (overlapped Schur tile batches); they are added when the columns become the panel.  The
-  // appended rhs row (row n) has no S2 row.
   if (has_row) {
     const double* Arow = A + (size_t)row * n + k0;
 #pragma unroll
     for (int c = 0; c < 2 * NB; ++c) x[c] = Arow[c];
-    if (S2 && row < n) {
-      const double* Srow = S2 + (size_t)row * n + k0;
-#pragma unroll
-      for (int c = 0; c < 2 * NB; ++c) x[c] += Srow[c];
-    }
   } else if (wave == 1 && lane < NB) {
     const double* Arow = A + (size_t)(k0 + NB + lane) * n + k0;
 #pragma unroll
     for (int c = 0; c < NB; ++c) x[c] = Arow[c];
-    if (S2) {
-      const double* Srow = S2 + (size_t)(k0 + NB + lane) * n + k0;
-#pragma unroll
-      for (int c = 0; c < NB; ++c) x[c] += Srow[c];
-    }
 #pragma unroll
     for (int c = NB; c < 2 * NB; ++c) x[c] = 0.0;
   } else {
@@ -580,10 +269,10 @@ __global__ __launch_bounds__(256) void chol_panel2_kernel(double* __restrict__ A
   for (int e = tid; e < NB * NB; e += 256) {
     const int i = e / NB, c = e % NB;
     const size_t o1 = (size_t)(k0 + i) * n + k0 + c, o2 = (size_t)(k0 + NB + i) * n + k0 + NB + c;
-    D1[i * LD + c] = (c <= i) ? A[o1] + (S2 ? S2[o1] : 0.0) : 0.0;
-    D2[i * LD + c] = (c <= i) ? A[o2] + (S2 ? S2[o2] : 0.0) : 0.0;
+    D1[i * LD + c] = (c <= i) ? A[o1] : 0.0;
+    D2[i * LD + c] = (c <= i) ? A[o2] : 0.0;
   }
-  FACTOR_DIAG(D1, rd1, (blockIdx.x == 0) ? fail : nullptr);
+  factor_diag_lds4<NB, false>(D1, nullptr, rd1, fscr, (blockIdx.x == 0) ? fail : nullptr);
   // first block column: panel rows (wave 0) and the 32 rows of L21 (wave 1) through L11
   if (wave <= 1) {
     double (&x1)[NB] = reinterpret_cast<double (&)[NB]>(x);
@@ -604,7 +293,7 @@ __global__ __launch_bounds__(256) void chol_panel2_kernel(double* __restrict__ A
       D2[i * LD + c] -= s0 + s1;
     }
   }
-  FACTOR_DIAG(D2, rd2, (blockIdx.x == 0) ? fail : nullptr);
+  factor_diag_lds4<NB, false>(D2, nullptr, rd2, fscr, (blockIdx.x == 0) ? fail : nullptr);
   if (blockIdx.x == 0) {
     for (int e = tid; e < NB * NB; e += 256) {
       const int i = e / NB, c = e % NB;
@@ -887,9 +576,6 @@ __device__ __forceinline__ double ld_agent(const double* p) {
 // buffer of their own (`xpub`, behind the launch-order map) that the forward launch has filled with a sentinel -- a NaN pattern no
 // solve produces -- and every consumer lane polls ITS element until it is no longer the sentinel: one memory round trip per
 // hand-off instead of two (flag observed, then the values fetched), and no store drain + flag on the producer's side.
-#ifndef VGG_BW_SENTINEL
-#define VGG_BW_SENTINEL 1
-#endif
 constexpr unsigned long long kXSentinel = 0x7FF8C0DEC0DE0001ull;
 __host__ __device__ inline double* df_xpub(int32_t* flags, int nbk) {
   const size_t ints = (size_t)(nbk + 1) * nbk + 3 * (size_t)nbk + 1 + ((size_t)nbk * (nbk + 1) / 2 + nbk);   // flags | map
@@ -928,55 +614,6 @@ __device__ unsigned long long* g_chol_trace = nullptr;      // [tiles][8] wall-c
 #define DF_STAMP_AT(tile, slot) do { } while (0)
 #endif
 #define DF_STAMP(slot) DF_STAMP_AT(nat_tile, slot)
-
-// 32 x 32 x 32 product on the matrix cores by the four wavefronts of a workgroup, operands read from LDS through
-// accessors: out(i, j) <- sum_k opA(i, k) * opB(j, k); wavefront w owns the 16 x 16 tile (w >> 1, w & 1).
-template <class FA, class FB, class FO>
-__device__ __forceinline__ void mm32_lds(FA opA, FB opB, FO out) {
-  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ti = wave >> 1, tj = wave & 1;
-  f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int s = 0; s < 8; ++s)
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(opA(16 * ti + li, 4 * s + lk), opB(16 * tj + li, 4 * s + lk), acc, 0, 0, 0);
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) out(16 * ti + lk + 4 * reg, 16 * tj + li, acc[reg]);
-}
-
-// 64 x 64 diagonal block (LDS, ld = 65, lower triangle valid) -> its factor in place and T = L^-T (upper triangular) in
-// Tl, as two 32 x 32 factorisations (factor_diag_lds4) glued by four small matrix-core products:
-//   L21 = D21 T11,  D22 -= L21 L21^T,  T12 = -T11 (L21^T T22).
-// (One 64-wide factor_diag_lds4 was measured at 40 us: its rank-4 trailing updates are LDS-issue bound.)
-#ifdef VGG_CHOL_LOOKAHEAD                          // opt-in experiment (measured slower, see factor_diag_lds4_la)
-#define FACTOR32(Dp, Tp, rdp, scrp, failp) factor_diag_lds4_la<H, true, LD>(Dp, Tp, rdp, scrp, failp)
-#else
-#define FACTOR32(Dp, Tp, rdp, scrp, failp) factor_diag_lds4<H, true, LD>(Dp, Tp, rdp, scrp, failp)
-#endif
-__device__ __forceinline__ void factor64(double* D, double* Tl, double* rd, double* scr, int32_t* fail) {
-  constexpr int LD = DFB + 1, H = 32;
-  const int tid = threadIdx.x;
-  FACTOR32(D, Tl, rd, scr, fail);
-  double v[4];
-  int vi[4], vj[4], cnt = 0;
-  mm32_lds([&](int i, int k) { return D[(H + i) * LD + k]; }, [&](int j, int k) { return Tl[k * LD + j]; },
-           [&](int i, int j, double x) { v[cnt] = x; vi[cnt] = i; vj[cnt] = j; ++cnt; });
-  __syncthreads();                                       // every wavefront has read D21 before anyone overwrites it
-#pragma unroll
-  for (int q = 0; q < 4; ++q) D[(H + vi[q]) * LD + vj[q]] = v[q];
-  for (int e = tid; e < H * H; e += 256) Tl[(H + e / H) * LD + e % H] = 0.0;           // T21 = 0
-  __syncthreads();
-  mm32_lds([&](int i, int k) { return D[(H + i) * LD + k]; }, [&](int j, int k) { return D[(H + j) * LD + k]; },
-           [&](int i, int j, double x) { if (j <= i) D[(H + i) * LD + H + j] -= x; });
-  FACTOR32(D + H * LD + H, Tl + H * LD + H, rd + H, scr, fail);
-  double* W = scr;                                       // 32 x 32
-  mm32_lds([&](int i, int k) { return D[(H + k) * LD + i]; }, [&](int j, int k) { return Tl[(H + k) * LD + H + j]; },
-           [&](int i, int j, double x) { W[i * H + j] = x; });
-  __syncthreads();
-  mm32_lds([&](int i, int k) { return Tl[i * LD + k]; }, [&](int j, int k) { return W[k * H + j]; },
-           [&](int i, int j, double x) { Tl[i * LD + H + j] = -x; });
-  __syncthreads();
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Round 3: the 64 x 64 diagonal block as FOUR 16 x 16 blocks (blocked right-looking), instead of two 32 x 32 ones.
@@ -1038,35 +675,8 @@ __device__ __forceinline__ f64x4 load_block16_sym(const double* D, int kb) {
   return acc;
 }
 
-// Round 6, three formulations of the step MEASURED AND NOT ADOPTED (compile-time switches, defaults = the round-5 step;
-// scripts/ubench/factor64_bench, profiles/r06_ab_factor16_variants.jsonl -- one 64 x 64 block, same box):
-//   VGG_F16_LA = 1 / 2 / 4 -- look-ahead: the first LA rows of the NEXT 4 x 4 pivot block are brought up to date by every lane
-//     redundantly, in scalar arithmetic, from values broadcast at the start of the step, so that the next reciprocal chain
-//     starts one multiply-add behind r3 instead of behind two matrix instructions and ten broadcasts: 9.63 -> 10.3 / 11.2 /
-//     13.2 us.  What it takes off the dependent chain (~100 cycles for LA = 1: the first reciprocal only -- the other nine
-//     values still arrive through the update) it puts back as ~30 more instructions per step in a wavefront that issues in
-//     order.
-//   VGG_F16_SQ = 1 -- d_{t+1} takes its last term as (u^2) r_t, one operation behind r_t instead of two: inside the noise.
-//   VGG_F16_BCAST = 1 / 2 -- the pivot block broadcast through the LDS crossbar (ds_bpermute_b32, result in a VECTOR register:
-//     an fp64 instruction takes one scalar operand, and a step spends 14 v_mov_b32 on carrying v_readlane results back):
-//     123 -> 95 instructions per step and 9.53 -> 10.1 / 10.3 us -- the crossbar's round trip in front of every pivot chain
-//     costs more than the moves.
-//   -mllvm -amdgpu-mfma-vgpr-form (no AGPR copies around the matrix instructions, 123 -> 105 instructions): 9.68 -> 9.53 us.
-// Reading: a step is ~850 cycles of dependent fp64 latency (four reciprocal chains, two matrix instructions, the broadcast)
-// plus the issue slots of whatever else is in the stream; removing cheap instructions buys little, and nothing found shortens
-// the dependent part without adding more than it removes.  The 64 x 64 block stays at 9.6 us, the block column at 14 us.
-#ifndef VGG_F16_LA
-#define VGG_F16_LA 0
-#endif
-#ifndef VGG_F16_SQ
-#define VGG_F16_SQ 0
-#endif
-#ifndef VGG_F16_BCAST
-#define VGG_F16_BCAST 0
-#endif
-template <int LD, int LA = VGG_F16_LA, bool SQ = (VGG_F16_SQ != 0)>
+template <int LD>
 __device__ __forceinline__ bool factor16_mfma(f64x4 acc, double* D, double* Tl, int kb) {
-  static_assert(LA >= 0 && LA <= 4, "rows of the next pivot block taken ahead");
   const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
   double* Db = D + (16 * kb) * LD + 16 * kb;
   double* Tb = Tl + (16 * kb) * LD + 16 * kb;
@@ -1085,76 +695,35 @@ __device__ __forceinline__ bool factor16_mfma(f64x4 acc, double* D, double* Tl, 
   const double k12 = (li == 2 && lk == 1) ? 1.0 : 0.0, k13 = (li == 3 && lk == 1) ? 1.0 : 0.0, k23 = (li == 3 && lk == 2) ? 1.0 : 0.0;
   const double kone = (li < 4 && lk == li) ? 1.0 : 0.0;
   const double q0 = (lk == 0) ? 1.0 : 0.0, q1 = (lk == 1) ? 1.0 : 0.0, q2 = (lk == 2) ? 1.0 : 0.0, q3 = (lk == 3) ? 1.0 : 0.0;
-  double pl[4][4] = {};                              // rows < LA of the next pivot block, taken ahead (lower triangle)
+  // (an opaque zero held in a vector register through the four steps, left from a broadcast experiment: without it the
+  //  register allocation of chol_dataflow_kernel comes out differently, so it goes in a change that re-measures the kernel)
   int vzero = 0;
-  asm volatile("" : "+v"(vzero));                    // (a vector register the compiler cannot fold: bpermute_f64)
-  (void)vzero;
+  asm volatile("" : "+v"(vzero));
 #pragma unroll
   for (int j0 = 0; j0 < 16; j0 += 4) {
     const int qq = j0 / 4;
     const double pa = acc[qq], pe = accE[qq];
-    // p_ab = A[j0 + a][j0 + b] is register acc[qq] of lane (li = j0 + a, lk = b) -- or was taken ahead by the previous step
-#if VGG_F16_BCAST == 0
-#define VGG_BC(v, l) readlane_f64(v, l)
-#elif VGG_F16_BCAST == 1
-#define VGG_BC(v, l) bpermute_f64(v, l, vzero)
-#else                                                // 2: the first pivot by v_readlane (its reciprocal starts the chain), the rest through LDS
-#define VGG_BC(v, l) (((l) == j0) ? readlane_f64(v, l) : bpermute_f64(v, l, vzero))
-#endif
-#define VGG_P(a, b) ((j0 > 0 && (a) < LA) ? pl[a][b] : VGG_BC(pa, j0 + (a) + 16 * (b)))
+    // p_ab = A[j0 + a][j0 + b] is register acc[qq] of lane (li = j0 + a, lk = b)
+#define VGG_P(a, b) readlane_f64(pa, j0 + (a) + 16 * (b))
     const double d0 = VGG_P(0, 0);
     const double r0 = fast_rcp<1>(d0);
     const double u10 = VGG_P(1, 0), p11 = VGG_P(1, 1);
     const double u20 = VGG_P(2, 0), p21 = VGG_P(2, 1), p22 = VGG_P(2, 2);
     const double u30 = VGG_P(3, 0), p31 = VGG_P(3, 1), p32 = VGG_P(3, 2), p33 = VGG_P(3, 3);
 #undef VGG_P
-#undef VGG_BC
-    // inputs of the look-ahead: row j0 + 4 + a of this panel (c) and of the next pivot block (e), as they stand
-    constexpr int LAR = LA > 0 ? LA : 1;
-    double cx[LAR][4], ce[LAR][LAR];
-    const bool ahead = LA > 0 && j0 < 12;
-    if (ahead) {
-      const double pn = acc[(qq + 1) & 3];
-#pragma unroll
-      for (int a = 0; a < LA; ++a) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) cx[a][b] = readlane_f64(pa, j0 + 4 + a + 16 * b);
-#pragma unroll
-        for (int b = 0; b <= a; ++b) ce[a][b] = readlane_f64(pn, j0 + 4 + a + 16 * b);
-      }
-    }
     // the scale of this lane's column of the PREVIOUS step: one short chain per lane in the shadow of the matrix instructions
     if (j0 > 0) fast_rsqrt_sqrt(dlast, rs[qq - 1], sd[qq - 1]);
     const double m10 = u10 * r0, m20 = u20 * r0, m30 = u30 * r0;        // multipliers a_cj / d_j
-    const double d1 = SQ ? __builtin_fma(-(u10 * u10), r0, p11) : p11 - u10 * m10;
+    const double d1 = p11 - u10 * m10;
     const double u21 = p21 - u20 * m10, u31 = p31 - u30 * m10;
     const double r1 = fast_rcp<1>(d1);
     const double m21 = u21 * r1, m31 = u31 * r1;
-    const double d2 = SQ ? __builtin_fma(-(u21 * u21), r1, p22 - u20 * m20) : (p22 - u20 * m20) - u21 * m21;
+    const double d2 = (p22 - u20 * m20) - u21 * m21;
     const double u32 = (p32 - u30 * m20) - u31 * m21;
     const double r2 = fast_rcp<1>(d2);
     const double m32 = u32 * r2;
-    const double d3 = SQ ? __builtin_fma(-(u32 * u32), r2, (p33 - u30 * m30) - u31 * m31) : ((p33 - u30 * m30) - u31 * m31) - u32 * m32;
+    const double d3 = ((p33 - u30 * m30) - u31 * m31) - u32 * m32;
     const double r3 = fast_rcp<1>(d3);
-    if (ahead) {
-      double xs[LAR][4];
-#pragma unroll
-      for (int a = 0; a < LA; ++a) {
-        xs[a][0] = cx[a][0];
-        xs[a][1] = cx[a][1] - xs[a][0] * m10;
-        xs[a][2] = (cx[a][2] - xs[a][0] * m20) - xs[a][1] * m21;
-        xs[a][3] = ((cx[a][3] - xs[a][0] * m30) - xs[a][1] * m31) - xs[a][2] * m32;
-      }
-#pragma unroll
-      for (int a = 0; a < LA; ++a)
-#pragma unroll
-        for (int b = 0; b <= a; ++b) {
-          double v = __builtin_fma(-(xs[a][0] * xs[b][0]), r0, ce[a][b]);
-          v = __builtin_fma(-(xs[a][1] * xs[b][1]), r1, v);
-          v = __builtin_fma(-(xs[a][2] * xs[b][2]), r2, v);
-          pl[a][b] = __builtin_fma(-(xs[a][3] * xs[b][3]), r3, v);
-        }
-    }
     // x_t = sum_k a_k W[k][t]:  W[k][t] = -sum_{k <= s < t} W[k][s] m_ts,  W[k][k] = 1
     const double w02 = __builtin_fma(m10, m21, -m20), w13 = __builtin_fma(m21, m32, -m31);
     const double w03 = __builtin_fma(-w02, m32, __builtin_fma(m10, m31, -m30));
@@ -1245,7 +814,7 @@ __device__ __forceinline__ void factor64_blocked(double* D, double* Tl, double* 
         }
     }
     // (kb == 0: every global store this wavefront issued before the factorisation has left the CU -- free here, 2 us after
-    //  the last of them; the caller's `slab(0)` may then publish what they wrote: VGG_DF_LATE_XFLAG)
+    //  the last of them; the caller's `slab(0)` may then publish what they wrote)
     if (kb == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                 // L_kk, T_kk and every update of step kb - 1 are in LDS
     // panels: L[ib][kb] = D[ib][kb] T_kk (ib > kb), E[ib][kb] = E[ib][kb] T_kk (ib < kb): three products.
@@ -1292,9 +861,6 @@ constexpr int kDfOrderMax = 64;               // block columns up to which the c
 // which used to return at once -- applies the updates k <= c - 1 of tile (c+1, c+1), leaves the partial tile in place and raises
 // dready[c+1]; the merged workgroup adds only X X^T (k = c) and factors.  The sums are associated differently (the partial
 // tile first, X X^T last): results move in the last bits against round 5; a solve stays bit-reproducible.
-#ifndef VGG_DF_SPLIT_DIAG
-#define VGG_DF_SPLIT_DIAG 1
-#endif
 
 struct DfShared {
   double D[DFB * (DFB + 1)];
@@ -1359,18 +925,16 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
     return (split_b > 0 && br < nbk && DFB * br >= split_a && DFB * (br + 1) <= split_a + split_b) ? split_a / DFB : 0;
   };
   if (c < first_of(r)) return;                          // structurally zero tile (block-diagonal leading part)
-  if (VGG_BW_SENTINEL && r == nbk && threadIdx.x < DFB)    // (the backward launch's hand-off buffer: see kXSentinel)
+  if (r == nbk && threadIdx.x < DFB)    // (the backward launch's hand-off buffer: see kXSentinel)
     reinterpret_cast<unsigned long long*>(df_xpub(flags, nbk))[DFB * c + threadIdx.x] = kXSentinel;
   const bool diag = (r == c);
   // the diagonal tile of column x is finished by the workgroup of tile (x, x - 1)
   auto chained = [&](int x) { return CHAIN && x >= 1 && x < nbk && first_of(x) <= x - 1; };
-  const bool prep = VGG_DF_SPLIT_DIAG && diag && chained(c);      // diagonal tile finished elsewhere: this workgroup applies its early updates
-  if (!VGG_DF_SPLIT_DIAG && diag && chained(c)) return;
+  const bool prep = diag && chained(c);                 // diagonal tile finished elsewhere: this workgroup applies its early updates
   const bool merged = CHAIN && !diag && r == c + 1 && chained(r);
   // (two workgroups per CU: the ones on the pivot chain -- diagonal tiles and the merged first sub-diagonal ones -- go first)
   if (df_occupancy(CHAIN) > 1 && (diag || merged)) __builtin_amdgcn_s_setprio(3);
   const int kfirst = max(first_of(r), first_of(c));
-  const int kstart = (merged && !VGG_DF_SPLIT_DIAG) ? first_of(r) : kfirst;     // (the diagonal tile (r,r) starts at the row's own envelope)
   const int kend = prep ? c - 1 : c;                    // (a prepared diagonal tile leaves update k = c - 1 = X X^T to the merged workgroup)
   int32_t* ready = flags;
   int32_t* tready = flags + (size_t)(nbk + 1) * nbk;
@@ -1430,10 +994,8 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
           const int i = 32 * wy + 16 * m + lk + 4 * reg, j = 32 * wx + 16 * q + li;
-          if (VGG_DF_SPLIT_DIAG)                        // (written by the diagonal tile's workgroup during this launch)
-            a0d[m][q][reg] = (merged && i < vr && j < vr && j <= i) ? ld_agent(&A[(size_t)(r0 + i) * n + r0 + j]) : 0.0;
-          else
-            a0d[m][q][reg] = (merged && i < vr && j < vr && j <= i) ? A[(size_t)(r0 + i) * n + r0 + j] : 0.0;
+          // (written by the diagonal tile's workgroup during this launch)
+          a0d[m][q][reg] = (merged && i < vr && j < vr && j <= i) ? ld_agent(&A[(size_t)(r0 + i) * n + r0 + j]) : 0.0;
         }
   };
 
@@ -1472,7 +1034,7 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
   // (~3 us at 50 block columns, hidden behind its first wait); past kDfOrderMax block columns the launch is bound by the
   // number of resident workgroups and those microseconds would add up (c5, 94 block columns: +6 %), so the order stays
   // ascending there.
-  const int nupd = max(kend - kstart, 0);
+  const int nupd = max(kend - kfirst, 0);
   const bool by_depth = CHAIN && nupd >= 2 && nbk <= kDfOrderMax;
   if (by_depth) {
     if (wave == 0) {
@@ -1486,9 +1048,9 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
         if (lane == 0) dep[k] = m + 1;
       }
       for (int idx = lane; idx < nupd; idx += 64) {
-        const int k = kstart + idx, dk = dep[k];
+        const int k = kfirst + idx, dk = dep[k];
         int rank = 0;
-        for (int k2 = kstart; k2 < kend; ++k2) { const int d2 = dep[k2]; rank += (d2 < dk) || (d2 == dk && k2 < k); }
+        for (int k2 = kfirst; k2 < kend; ++k2) { const int d2 = dep[k2]; rank += (d2 < dk) || (d2 == dk && k2 < k); }
         sh.order[rank] = k;
       }
     }
@@ -1496,21 +1058,11 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
   }
   if (nupd <= 0) load_a0();
   // left-looking updates: acc += L[r][k] L[c][k]^T  (merged: and accd += L[r][k] L[r][k]^T)
-  // -DVGG_DF_PREFETCH=1 (round 6, MEASURED, off): the operand tiles of update t + 1 requested BEFORE the matrix instructions of
-  // update t whenever their flags are already up (a relaxed look, no wait; every wavefront decides for itself -- it stages its own
-  // rows -- and waits alone where it has to), written to LDS behind them.  The idea: at n = 3200 a block column takes 18-21 us
-  // against the 14 us of the pivot chain, and a tile works through ~40 updates of 3.2 us (round trip + matrix instructions) with
-  // ~5 block columns resident ahead.  scripts/ubench/chol_bench, same box, two rounds: n = 3200 0.926 -> 0.913 ms, with the
-  // configs[3] camera split 0.826 -> 0.818, n = 1202 unchanged, n = 6002 dense 2.41 -> 2.63 (the extra loads in flight cost more
-  // than they hide there): the update queues are not what sets the step.  Same sums in the same order either way.
-#ifndef VGG_DF_PREFETCH
-#define VGG_DF_PREFETCH 0
-#endif
   {
     double* bufA = sh.D;
     double* bufB = diag ? sh.D : sh.T;
     double va[16], vb[16];
-    auto upd_k = [&](int t) { return by_depth ? sh.order[t] : kstart + t; };
+    auto upd_k = [&](int t) { return by_depth ? sh.order[t] : kfirst + t; };
     auto request = [&](int k) __attribute__((always_inline)) {
       const int k0 = DFB * k;
       const bool do_tile = k >= kfirst;
@@ -1520,15 +1072,6 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
         va[q] = (row < vr) ? ld_agent(&A[(size_t)(r0 + row) * n + k0 + col]) : 0.0;
         if (!diag) vb[q] = (do_tile && row < vc) ? ld_agent(&A[(size_t)(c0 + row) * n + k0 + col]) : 0.0;
       }
-    };
-    // are the operand tiles of update column k final?  (wave-uniform: lane 0 looks, everybody gets its answer)
-    auto flags_up = [&](int k) -> bool {
-      int up = 0;
-      if (lane == 0) {
-        up = __hip_atomic_load(&ready[(size_t)r * nbk + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 1;
-        if (up && !diag && k >= kfirst) up = __hip_atomic_load(&ready[(size_t)c * nbk + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 1;
-      }
-      return __builtin_amdgcn_readfirstlane(up) != 0;
     };
     // wait of ONE wavefront (lane 0 polls; bounded like df_wait_ge)
     auto wave_wait = [&](const int32_t* flag) {
@@ -1542,15 +1085,14 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
         }
       }
     };
-    bool have = false;                                   // this wavefront's registers hold the operands of the next update
     for (int t = 0; t < nupd; ++t) {
       const int k = upd_k(t);
       const bool do_tile = k >= kfirst;
-      if (!have) {                                       // (not requested ahead: wait for the flags, this wavefront alone -- it
-        wave_wait(&ready[(size_t)r * nbk + k]);          //  stages its own rows, and the barrier behind the LDS writes is the one
-        if (!diag && do_tile) wave_wait(&ready[(size_t)c * nbk + k]);   // all four meet at)
-        request(k);
-      }
+      // (wait for the flags, this wavefront alone -- it stages its own rows, and the barrier behind the LDS writes is the one
+      //  all four meet at)
+      wave_wait(&ready[(size_t)r * nbk + k]);
+      if (!diag && do_tile) wave_wait(&ready[(size_t)c * nbk + k]);
+      request(k);
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int row = (tid >> 6) + 4 * q, col = lane;
@@ -1558,14 +1100,8 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
         if (!diag) bufB[row * LD + col] = vb[q];
       }
       __syncthreads();
-      have = false;
-      if (VGG_DF_PREFETCH && t + 1 < nupd) {
-        const int kn = upd_k(t + 1);
-        if (flags_up(kn)) { request(kn); have = true; }
-      }
       if (t == nupd - 1) load_a0();                      // (in flight behind the matrix instructions below)
       if (do_tile) multiply_staged(bufA, bufB, acc);
-      if (merged && !VGG_DF_SPLIT_DIAG) multiply_staged(bufA, bufA, accd);
       __syncthreads();                                   // operands consumed: the buffers may be refilled
     }
   }
@@ -1605,20 +1141,10 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
   // (which nobody waits for: it only matters through T_b and as output)
   // T is handed on in four slabs of 16 columns, tready[bc] = number of slabs out: the tiles of the column multiply by the
   // first three while the factorisation is still running (columns 16 kb .. of T are final after step kb)
-  auto factor_and_publish = [&](int bc, int b0, int vb, int trace_tile, int32_t* late_flag) __attribute__((always_inline)) {
+  auto factor_and_publish = [&](int bc, int b0, int vb, int trace_tile) __attribute__((always_inline)) {
     (void)trace_tile;
     double* Tg = Tinv + (size_t)bc * DFB * DFB;
-#ifdef VGG_CHOL_PAIRS                              // A/B: the round-2 form, two 32 x 32 blocks, T in one piece
-    factor64(sh.D, sh.T, sh.rd, sh.scr, fail);
-    DF_STAMP_AT(trace_tile, 2);                          // factored
-    for (int e = tid; e < DFB * DFB; e += 256) {
-      const int i = e / DFB, j = e % DFB;
-      st_agent(&Tg[e], (j >= i) ? sh.T[i * LD + j] : 0.0);
-    }
-#else
     factor64_blocked(sh.D, sh.T, sh.scr, fail, [&](int kb) {
-      // (the flag of the merged workgroup's sub-diagonal tile: its stores were drained in front of the first barrier inside)
-      if (kb == 0 && late_flag && lane == 0) __hip_atomic_store(late_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       // one wavefront: 64 rows x 16 columns (rows below the diagonal block are zero), its own drain, then the count
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
@@ -1633,21 +1159,16 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
       const int i = e / 16, j = 48 + e % 16;
       st_agent(&Tg[i * DFB + j], sh.T[i * LD + j]);
     }
-#endif
     df_publish(&tready[bc], 4);
     DF_STAMP_AT(trace_tile, 3);                          // published
     for (int e = tid; e < DFB * DFB; e += 256) {
       const int i = e / DFB, j = e % DFB;
-#ifdef VGG_DF_L_AGENT
-      if (j <= i && i < vb) st_agent(&A[(size_t)(b0 + i) * n + b0 + j], sh.D[i * LD + j]);
-#else
       if (j <= i && i < vb) A[(size_t)(b0 + i) * n + b0 + j] = sh.D[i * LD + j];
-#endif
     }
     // (ready[b][b] is never waited for: L_bb only matters through T_b)
   };
   if (diag) {
-    factor_and_publish(c, c0, vc, nat_tile, nullptr);
+    factor_and_publish(c, c0, vc, nat_tile);
     return;
   }
 
@@ -1660,7 +1181,7 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb) {
     if (kb == 3 && merged) {                             // (the diagonal tile's values: needed behind the last slab)
-      if (VGG_DF_SPLIT_DIAG) df_wait(&dready[r], fail);    // (raised long ago: its last operand is a tile of column c - 1)
+      df_wait(&dready[r], fail);                         // (raised long ago: its last operand is a tile of column c - 1)
       load_a0d();
     }
     df_wait_ge(&tready[c], kb + 1, fail);
@@ -1721,20 +1242,10 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
         if (i >= vr || j >= vr) v = (i == j) ? 1.0 : 0.0;
         sh.D[i * LD + j] = v;
       }
-  // -DVGG_DF_LATE_XFLAG=1 (measured twice, off): the flag of tile (r, c) = X raised from INSIDE the factorisation, behind its
-  // first 16 x 16 step, where the drain of the X stores is free -- 0.7 us off the factor path, but the flag is ~2.4 us late for
-  // tile (r+1, r), whose wait for it + last update + first three slab products are a second chain per block column.  Round 4:
-  // 0.273 -> 0.294 ms at n = 1202.  Round 6, with that tile's workgroup relieved of the diagonal tile's update queue
-  // (VGG_DF_SPLIT_DIAG: its chain ~11.5 us against the 14.3 of the factor path): 0.260 -> 0.286 ms at n = 1202, 0.797 -> 0.868
-  // at n = 3200 -- the block column goes to 16 us: 11.5 + 2.4 + the slab it then waits for is past the factor path again.
-#ifndef VGG_DF_LATE_XFLAG
-#define VGG_DF_LATE_XFLAG 0
-#endif
-  if (VGG_DF_LATE_XFLAG) lds_barrier();                   // (the reads of X in sh.T are through; the diagonal tile's value is in sh.D)
-  else df_publish(&ready[(size_t)r * nbk + c]);
+  df_publish(&ready[(size_t)r * nbk + c]);
   DF_STAMP(3);
   DF_STAMP_AT(dtile, 1);                                 // diagonal tile r: updates applied
-  factor_and_publish(r, r0, vr, dtile, VGG_DF_LATE_XFLAG ? &ready[(size_t)r * nbk + c] : nullptr);
+  factor_and_publish(r, r0, vr, dtile);
 }
 
 // Backward substitution L^T x = z in dataflow form: one workgroup per 64-column block c (launched last block first, so
@@ -1778,25 +1289,20 @@ __global__ __launch_bounds__(256) void chol_backward_dataflow_kernel(const doubl
     int rn = r - 1;
     while (rn > c && first_of(rn) > c) --rn;
     if (rn > c) load_tile(rn, nxt);                       // in flight while this workgroup waits for x_r
-    if (VGG_BW_SENTINEL) {
-      if (tid < DFB) {
-        double v = 0.0;
-        if (DFB * r + tid < n) {
-          int spins = 0;
-          for (;;) {
-            v = ld_agent(&xpub[DFB * r + tid]);
-            if ((unsigned long long)__double_as_longlong(v) != kXSentinel) break;
-            __builtin_amdgcn_s_sleep(1);
-            ++spins;
-            const bool lost = fail && (spins & 1023) == 0 && __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 2;
-            if (spins > kSpinLimit || lost) { if (fail) __hip_atomic_store(fail, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); v = 0.0; break; }
-          }
+    if (tid < DFB) {
+      double v = 0.0;
+      if (DFB * r + tid < n) {
+        int spins = 0;
+        for (;;) {
+          v = ld_agent(&xpub[DFB * r + tid]);
+          if ((unsigned long long)__double_as_longlong(v) != kXSentinel) break;
+          __builtin_amdgcn_s_sleep(1);
+          ++spins;
+          const bool lost = fail && (spins & 1023) == 0 && __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 2;
+          if (spins > kSpinLimit || lost) { if (fail) __hip_atomic_store(fail, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); v = 0.0; break; }
         }
-        xs[tid] = v;
       }
-    } else {
-      df_wait(&xready[r], fail);
-      if (tid < DFB) xs[tid] = (DFB * r + tid < n) ? ld_agent(&b[DFB * r + tid]) : 0.0;
+      xs[tid] = v;
     }
     __syncthreads();
 #pragma unroll
@@ -1821,10 +1327,8 @@ __global__ __launch_bounds__(256) void chol_backward_dataflow_kernel(const doubl
   __syncthreads();
   if (tid < vc) {
     const double xv = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-    if (VGG_BW_SENTINEL) { st_agent(&xpub[c0 + tid], xv); b[c0 + tid] = xv; }
-    else st_agent(&b[c0 + tid], xv);
+    st_agent(&xpub[c0 + tid], xv); b[c0 + tid] = xv;
   }
-  if (!VGG_BW_SENTINEL) df_publish(&xready[c]);
 }
 
 // LAUNCH ORDER with a row envelope.  In (column, row) order the tiles of a pivot chain that starts late in the matrix
@@ -1857,7 +1361,7 @@ __global__ __launch_bounds__(256) void df_tile_map_kernel(const int32_t* __restr
   __syncthreads();
   for (int c = tid; c < nbk; c += 256) {
     int n = 0;
-    for (int r = c; r <= nbk; ++r) n += (fo[r] <= c) && (VGG_DF_SPLIT_DIAG || !(r == c && chained(c)));
+    for (int r = c; r <= nbk; ++r) n += (fo[r] <= c);
     cnt[c] = n;
   }
   __syncthreads();
@@ -1871,7 +1375,7 @@ __global__ __launch_bounds__(256) void df_tile_map_kernel(const int32_t* __restr
   for (int c = tid; c < nbk; c += 256) {
     int o = off[c];
     for (int r = c; r <= nbk; ++r)
-      if ((fo[r] <= c) && (VGG_DF_SPLIT_DIAG || !(r == c && chained(c)))) map[1 + o++] = c | (r << 16);
+      if (fo[r] <= c) map[1 + o++] = c | (r << 16);
   }
   if (tid == 0) { int tot = 0; for (int c = 0; c < nbk; ++c) tot += cnt[c]; map[0] = tot; }
 }
@@ -1901,30 +1405,20 @@ static inline int block_size_for(int n) { (void)n; return 32; }
 // workspace = the inverted diagonal blocks T_j = L_jj^-T, NB x NB doubles each
 size_t cholesky_workspace_bytes(int n) {
   const int nb = block_size_for(n);
-  const size_t legacy = (size_t)div_up(n, nb) * nb * nb * sizeof(double) + 256;
+  const size_t multi = (size_t)div_up(n, nb) * nb * nb * sizeof(double) + 256;   // (the separate-right-hand-side solver)
   const size_t df = dataflow_workspace_bytes(n);
-  return legacy > df ? legacy : df;
-}
-
-// VGG_CHOL_LEGACY=1 in the environment selects the multi-launch path (A/B measurements)
-static bool use_dataflow(int n) {
-  static const bool legacy = [] { const char* e = getenv("VGG_CHOL_LEGACY"); return e && e[0] == '1'; }();
-  // (round 6: every size -- rounds 3-5 kept the multi-launch path below two 64-blocks, where it is 1.2-1.9 x slower: 76 -> 39 us
-  //  at the n = 102 of a 17-frame video window, 44 -> 25 at n = 54; VGG_DF_MIN_N restores a threshold for A/B measurements)
-  static const int min_n = [] { const char* e = getenv("VGG_DF_MIN_N"); return e ? atoi(e) : 1; }();
-  return !legacy && n >= min_n;
+  return multi > df ? multi : df;
 }
 
 // raises one overlap flag (a launch of its own behind a tile batch: the batch's stores are then visible device-wide)
 __global__ void df_signal_kernel(int32_t* flag) { __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 void dataflow_signal(int32_t* flag, hipStream_t st) { df_signal_kernel<<<1, 1, 0, st>>>(flag); }
 
-// The flags of the dataflow factorisation inside `ws` (nullptr when a system of n unknowns takes the multi-launch path).  A
-// caller that zeroes them itself -- *count int32, any time between the previous solve in this workspace and the next one
-// (bundle adjustment: in a kernel it launches anyway) -- passes flags_cleared = true and saves the fill launch.
+// The flags of the dataflow factorisation inside `ws`.  A caller that zeroes them itself -- *count int32, any time between
+// the previous solve in this workspace and the next one (bundle adjustment: in a kernel it launches anyway) -- passes
+// flags_cleared = true and saves the fill launch.
 int32_t* cholesky_dataflow_flags(double* ws, int n, size_t* count) {
-  if (!ws || !use_dataflow(n)) return nullptr;
-  if (count) *count = dataflow_flag_count(n);
+  *count = dataflow_flag_count(n);
   return reinterpret_cast<int32_t*>(ws + (size_t)div_up(n, DFB) * DFB * DFB);
 }
 
@@ -1933,11 +1427,10 @@ static int enqueue_dataflow(double* A, double* b, int n, double* ws, int32_t* de
   const int nbk = div_up(n, DFB);
   double* Tinv = ws;
   int32_t* flags = reinterpret_cast<int32_t*>(ws + (size_t)nbk * DFB * DFB);
-  // VGG_CHOL_CHAIN=0 / 1 in the environment: every diagonal tile in a workgroup of its own / chained (A/B measurements)
-  // (default: chained up to 64 block columns -- beyond, the dense left-looking update queue of a late column's workgroup
-  // is what the chain waits for, and a merged workgroup carries two of them; measured in DESIGN.md section 6)
-  static const int chain_env = [] { const char* e = getenv("VGG_CHOL_CHAIN"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
-  const int chain = chain_env >= 0 ? chain_env : (nbk <= kDfOrderMax ? 1 : 0);
+  // diagonal tiles chained up to 64 block columns, each in a workgroup of its own beyond -- there the dense left-looking
+  // update queue of a late column's workgroup is what the chain waits for, and a merged workgroup carries two of them
+  // (measured in DESIGN.md section 6)
+  const int chain = nbk <= kDfOrderMax ? 1 : 0;
   if (!flags_cleared && hipMemsetAsync(flags, 0, dataflow_flag_count(n) * sizeof(int32_t), st) != hipSuccess) return VGG_ERR_HIP;
   static bool attr_set = false;
   if (!attr_set) {
@@ -1950,10 +1443,9 @@ static int enqueue_dataflow(double* A, double* b, int n, double* ws, int32_t* de
   }
   if (!(split_a >= DFB && split_b >= DFB && split_a % DFB == 0 && split_a + split_b <= n)) split_a = split_b = 0;
   const int tiles = nbk * (nbk + 1) / 2 + nbk;
-  // launch order by dependency depth when the caller gave a row envelope (VGG_CHOL_TILE_MAP=0: the plain order, A/B)
-  static const bool map_on = [] { const char* e = getenv("VGG_CHOL_TILE_MAP"); return !(e && e[0] == '0'); }();
+  // launch order by dependency depth when the caller gave a row envelope
   int32_t* tile_map = nullptr;
-  if (first_blk && map_on && nbk <= kDfMapCols && !(overlap && overlap->dev_flags)) {
+  if (first_blk && nbk <= kDfMapCols && !(overlap && overlap->dev_flags)) {
     tile_map = flags + dataflow_flag_count(n);
     df_tile_map_kernel<<<1, 256, 0, st>>>(first_blk, nbk, chain, tile_map);
   }
@@ -1971,21 +1463,10 @@ static int enqueue_dataflow(double* A, double* b, int n, double* ws, int32_t* de
   return VGG_OK;
 }
 
-// If b is stored directly behind A (b == A + n*n, i.e. "row n" of an (n+1) x n matrix) the right-hand side
-// rides through the factorisation as one more panel row: the panel solve and the trailing update then
-// perform the forward substitution for free and only L^T y = z is left.
+// The separate-right-hand-side solver (b is NOT stored behind A: the dataflow kernel takes its right-hand side as row n of A
+// and cannot serve that call): the multi-launch factorisation described at the top of this file, then L z = b and L^T x = z.
 template <int NB>
-static int enqueue(double* A, double* b, int n, double* inv_blocks, int32_t* device_fail, const int32_t* skip,
-                   hipStream_t st, const CholOverlap* ov, int split_a, int split_b) {
-  int next_wait = 0;
-  // before the panel over columns [k0, k1): wait for the producers of those columns; S2 only where it can be non-zero
-  auto panel_s2 = [&](int k1) -> const double* {
-    if (!ov) return nullptr;
-    while (next_wait < ov->num_waits && ov->wait_col[next_wait] < k1) (void)hipStreamWaitEvent(st, ov->wait_ev[next_wait++], 0);
-    return (k1 > ov->first_col) ? ov->S2 : nullptr;
-  };
-  const bool fused_rhs = (b == A + (size_t)n * n);
-  const int nrows = fused_rhs ? n + 1 : n;
+static int enqueue(double* A, double* b, int n, double* inv_blocks, int32_t* device_fail, const int32_t* skip, hipStream_t st) {
   // fast backward solve: y and one T block in LDS (up to 150 KB); larger systems use the single-workgroup kernel
   const size_t back_lds = ((size_t)div_up(n, NB) * NB + NB * (NB + 1) + NB) * sizeof(double);
   bool lds_backward = back_lds <= 150 * 1024;
@@ -1994,67 +1475,47 @@ static int enqueue(double* A, double* b, int n, double* inv_blocks, int32_t* dev
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)back_lds) != hipSuccess)
       lds_backward = false;
   }
-  // one fused double step: 64 columns = one panel launch + one K = 64 trailing update
-  auto fused_step = [&](int k0, int k0_second) {
-    const int rows_panel = nrows - k0 - 64;
-    const double* S2 = panel_s2((k0_second >= 0 ? k0_second : k0) + 64);
-    const dim3 grid((rows_panel > 0 ? div_up(rows_panel, 64) : 1) + 1, k0_second >= 0 ? 2 : 1);
-    chol_panel2_kernel<<<grid, 256, 0, st>>>(A, n, nrows, k0, device_fail, skip, inv_blocks, S2, k0_second);
-    for (int which = 0; which < (k0_second >= 0 ? 2 : 1); ++which) {
-      const int k = which ? k0_second : k0;
-      const int rows_below = nrows - k - 64;
-      if (rows_below > 0 && k + 64 < n) {
-        const int T = div_up(rows_below, 32);
-        const int tiles = T * (T + 1) / 2;
-        chol_update_kernel<64><<<div_up(tiles, 4), 256, 0, st>>>(A, n, nrows, k, tiles, skip);
-      }
-    }
-  };
   int k0 = 0;
   if (NB == 32) {
-    // Block-diagonal leading part (split_a, split_b > 0): the column sets A = [0, split_a) and B = [split_a, split_a +
-    // split_b) do not couple (A[B rows][A cols] = 0 -- the caller ordered the unknowns that way, ba.py), so panel s of A
-    // and panel s of B are independent: they share one launch and their pivot chains run side by side.  The trailing
-    // updates stay separate launches (an A panel has zeros in the rows of B, so its update leaves B's columns
-    // bit-for-bit untouched).  What is left of A, then of B, then everything else follows in the usual order.
-    int lock = 0;
-    if (!ov && split_a >= 64 && split_b >= 64 && split_a % 64 == 0 && split_a + split_b <= n) lock = min(split_a, split_b) / 64;
-    for (int s2 = 0; s2 < lock; ++s2) fused_step(64 * s2, split_a + 64 * s2);
-    if (lock > 0) {
-      for (k0 = 64 * lock; k0 + 64 <= split_a; k0 += 64) fused_step(k0, -1);     // the rest of A (a multiple of 64)
-      k0 = split_a + 64 * lock;                                                  // the rest of B and everything behind it
+    // fused double steps while at least 64 columns remain: 64 columns = one panel launch + one K = 64 trailing update
+    for (; k0 + 64 <= n; k0 += 64) {
+      const int rows_below = n - k0 - 64;
+      chol_panel2_kernel<<<(rows_below > 0 ? div_up(rows_below, 64) : 1) + 1, 256, 0, st>>>(A, n, n, k0, device_fail, skip, inv_blocks);
+      if (rows_below > 0) {
+        const int T = div_up(rows_below, 32);
+        const int tiles = T * (T + 1) / 2;
+        chol_update_kernel<64><<<div_up(tiles, 4), 256, 0, st>>>(A, n, n, k0, tiles, skip);
+      }
     }
-    // fused double steps while at least 64 columns remain
-    for (; k0 + 64 <= n; k0 += 64) fused_step(k0, -1);
   }
   for (; k0 < n; k0 += NB) {
     const int nb = (n - k0 < NB) ? n - k0 : NB;
-    const int rows_panel = nrows - k0 - nb;
+    const int rows_panel = n - k0 - nb;
     const int grid = (rows_panel > 0 ? div_up(rows_panel, 256) : 1) + 1;
-    const double* S2 = panel_s2(k0 + nb);
-    chol_panel_kernel<NB><<<grid, 256, 0, st>>>(A, n, nrows, k0, device_fail, skip, inv_blocks, S2);
-    const int rows_below = nrows - k0 - NB;
-    if (rows_below > 0 && k0 + NB < n) {
+    chol_panel_kernel<NB><<<grid, 256, 0, st>>>(A, n, n, k0, device_fail, skip, inv_blocks);
+    const int rows_below = n - k0 - NB;
+    if (rows_below > 0) {
       const int T = div_up(rows_below, 32);
       const int tiles = T * (T + 1) / 2;
-      chol_update_kernel<NB><<<div_up(tiles, 4), 256, 0, st>>>(A, n, nrows, k0, tiles, skip);
+      chol_update_kernel<NB><<<div_up(tiles, 4), 256, 0, st>>>(A, n, n, k0, tiles, skip);
     }
   }
-  (void)panel_s2(n + 1);                        // (n == 0 cannot happen; every producer is waited for by now)
-  if (!fused_rhs) chol_solve_kernel<NB><<<1, 256, 0, st>>>(A, b, n, 1, lds_backward ? 0 : 1, skip);
-  else if (!lds_backward) chol_solve_kernel<NB><<<1, 256, 0, st>>>(A, b, n, 0, 1, skip);
+  chol_solve_kernel<NB><<<1, 256, 0, st>>>(A, b, n, 1, lds_backward ? 0 : 1, skip);
   if (lds_backward) chol_backward_kernel<NB><<<1, kBackThreads, back_lds, st>>>(A, b, n, inv_blocks, skip);
   if (hipGetLastError() != hipSuccess) return VGG_ERR_HIP;
   return VGG_OK;
 }
 
+// b stored directly behind A (b == A + n*n, i.e. "row n" of an (n+1) x n matrix: what bundle adjustment passes): the
+// single-launch dataflow factorisation, where the right-hand side rides through as one more tile row.  `overlap`, the split
+// and the envelope only exist there; with a separate b the system is factored in plain order.
 int cholesky_solve_enqueue(double* A, double* b, int n, double* inv_blocks, int32_t* device_fail, const int32_t* skip,
                            hipStream_t st, const CholOverlap* overlap, int split_a, int split_b, const int32_t* first_blk,
                            bool flags_cleared) {
   if (!inv_blocks) return VGG_ERR_INVALID_ARGUMENT;
-  if ((!overlap || overlap->dev_flags) && b == A + (size_t)n * n && use_dataflow(n))
+  if (b == A + (size_t)n * n)
     return enqueue_dataflow(A, b, n, inv_blocks, device_fail, skip, st, split_a, split_b, first_blk, overlap, flags_cleared);
-  return enqueue<32>(A, b, n, inv_blocks, device_fail, skip, st, overlap, split_a, split_b);
+  return enqueue<32>(A, b, n, inv_blocks, device_fail, skip, st);
 }
 
 }  // namespace vgg

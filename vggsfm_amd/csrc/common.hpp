@@ -58,17 +58,16 @@ __device__ __forceinline__ double load_f64(const T* p) { return (double)(*p); }
 inline int div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Overlap of the factorisation with the computation of the reduced system (ba.hip <-> chol.hip): contributions to
-// columns >= first_col arrive in a second matrix S2 (same n x n layout) from work running on another stream; event k
-// signals that every contribution to columns >= wait_col[k] (ascending) is in place.  The factorisation waits for
-// event k before the first panel that touches such a column and adds S2 to the panel when it loads it.
+// columns >= first_col arrive in a second matrix S2 (same n x n layout) from work running on another stream; device flag k
+// (set by a kernel behind each tile batch) says that every contribution to columns >= wait_col[k] (ascending) is in place.
+// The dataflow factorisation is one launch, so it waits on the device: a tile waits for the last flag its columns need and
+// adds S2 when it loads them.
 struct CholOverlap {
   const double* S2;
   int first_col;
   int num_waits;
   int wait_col[8];
-  hipEvent_t wait_ev[8];
-  const int32_t* dev_flags = nullptr;   // device [num_waits]: flag k != 0 <=> event k has happened (dataflow factorisation:
-                                        // one launch, so it waits on the device; set by a kernel behind each tile batch)
+  const int32_t* dev_flags = nullptr;   // device [num_waits]
 };
 // by-value kernel argument of the dataflow factorisation
 struct DfOverlap {
