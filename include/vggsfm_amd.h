@@ -485,6 +485,38 @@ int vgg_color_gather(const float* frames, int frame_begin, int frame_end, int he
 int vgg_color_reduce(const int64_t* obs_point, long num_obs, long num_points, const float* gathered, int64_t* point_ptr,
                      float* rgb, uint8_t* has_color, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Track video
+ *   Visualizer.draw_tracks_on_video   vggsfm/utils/visualizer.py:163-295, as runner.py:445-450 calls it
+ * All pointers are device memory.  T frames of height x width; the canvas is (height + 2 pad) x (width + 2 pad).
+ * Every track's prediction is drawn per frame as PIL's ellipse of integer radius r around its integer centre, in track
+ * order, opaque: a pixel ends with the colour of the highest track index whose stencil covers it.
+ *
+ * Owner pass over frames frame_begin .. frame_end-1 (at most 65535) of tracks (T, num_tracks, 2), float32 or float64
+ * (tracks_f64): centre = (int64)(coordinate + pad), the addition in the tracks' precision, truncated toward zero.  A
+ * track of a frame below query_frame, one whose integer x or y is 0, or whose coordinate is not finite or beyond 2^62
+ * draws nothing.  visibility (T, num_tracks) of vis_kind, or NULL with VGG_TRACK_VIS_NONE: a zero (-0.0 too) selects
+ * the outline stencil, anything else (a NaN included) the filled one.  stencil_rows: 2 x (2r + 1) uint32 in host
+ * memory, the filled stencil's rows then the outline's, row dy + r, bit dx + r.  owner (frame_end - frame_begin,
+ * canvas_h, canvas_w) uint32 (< 2^31 cells) is cleared by the entry and ends as track index + 1 of each pixel's
+ * winner, 0 where nothing was drawn.  num_tracks < 2^31 - 1, radius <= VGG_TRACK_MAX_RADIUS. */
+#define VGG_TRACK_MAX_RADIUS 15
+#define VGG_TRACK_VIS_NONE 0
+#define VGG_TRACK_VIS_U8 1
+#define VGG_TRACK_VIS_F32 2
+#define VGG_TRACK_VIS_F64 3
+int vgg_track_owner(const void* tracks, int tracks_f64, const void* visibility, int vis_kind, int frame_begin, int frame_end,
+                    int query_frame, long num_tracks, int pad, int canvas_h, int canvas_w, int radius,
+                    const uint32_t* stencil_rows, uint32_t* owner, void* stream);
+/* Resolve pass, after vgg_track_owner on the same frames: frames holds frames frame_begin .. frame_end-1 as
+ * (n, 3, height, width) float32 or uint8 (frames_u8).  Output pixel = the colour of its owner (colors[owner - 1], or
+ * colors[frame] with color_per_frame; r | g << 8 | b << 16), else the frame's pixel as uint8 (float: truncated, clamped
+ * to 0..255, NaN -> 0), else 255 in the border of pad.  out is the whole video (T - 1 + first_copies, 3, canvas_h,
+ * canvas_w) uint8: frame 0 is written first_copies (>= 1) times at its head, frame t > 0 at t - 1 + first_copies. */
+int vgg_track_resolve(const void* frames, int frames_u8, int frame_begin, int frame_end, int height, int width, int pad,
+                      const uint32_t* owner, const uint32_t* colors, int color_per_frame, int first_copies, uint8_t* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,7 @@ EXPORTED = ["vgg_build_arch", "vgg_abi_version", "vgg_abi_sizeof", "vgg_project_
             "vgg_fmat_eight_point", "vgg_fmat_residuals", "vgg_cholesky_solve_split", "vgg_ba_poll_done", "vgg_ba_tuning", "vgg_cholesky_solve_envelope", "vgg_ba_set_tile_rhs", "vgg_triangulate_tracks_chunks_enqueue",
             "vgg_sparse_depth", "vgg_depth_align_workspace_bytes", "vgg_depth_align", "vgg_depth_apply", "vgg_depth_unproject",
             "vgg_reproj_stats_workspace_bytes", "vgg_reproj_stats", "vgg_reproj_visible", "vgg_reproj_draw",
-            "vgg_color_gather", "vgg_color_reduce"]
+            "vgg_color_gather", "vgg_color_reduce", "vgg_track_owner", "vgg_track_resolve"]
 
 _lib = None
 

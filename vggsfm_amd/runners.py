@@ -35,6 +35,7 @@ class GeometryConfig:
     max_ransac_iters: int = 4096
     lo_num: int = 300
     visual_dense_point_cloud: bool = False
+    visual_tracks: bool = False
 
 
 def generate_grid_samples(rect, N=None, pixel_interval=None):
@@ -232,6 +233,20 @@ class GeometryRunner:
         predictions["depth_dict"] = depth_dict
         predictions["unproj_dense_points3D"] = unproj
         return predictions
+
+    # ------------------------------------------------------------------ track video (runner.py:445-450)
+    def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
+        """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
+        (vggsfm_amd.utils.visualizer.Visualizer, linewidth 1).  images (1,S,3,H,W) in [0, 1], pred_track (1,S,N,2),
+        pred_vis (1,S,N).  Returns the video (1, S + 2, 3, H, W) uint8 on the device; with `output_dir` it is also written
+        to output_dir/visuals/track.mp4 (needs imageio, see Visualizer.save_video)."""
+        import os
+
+        from .utils.visualizer import Visualizer
+
+        save_dir = "./results" if output_dir is None else os.path.join(output_dir, "visuals")
+        vis = Visualizer(save_dir=save_dir, linewidth=1)
+        return vis.visualize(images * 255, pred_track, pred_vis[..., None], filename="track", save_video=output_dir is not None)
 
     # ------------------------------------------------------------------ reprojection video (runner.py:834-885)
     def make_reprojection_video(self, predictions, video_size, image_paths, original_images):
