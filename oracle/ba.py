@@ -271,10 +271,11 @@ def normalize_reconstruction(ext, pts, pts_alive=None, extent=5.0, p0=0.1, p1=0.
 
 
 def pose_refinement(extrinsic, points2D, points3D, inlier_mask, intr_params, camera_type="SIMPLE_PINHOLE",
-                    refine_focal_length=True, refine_extra_params=True):
+                    refine_focal_length=True, refine_extra_params=True, options=None, loss=1, loss_scale=1.0):
     """pycolmap.pose_refinement (RefineAbsolutePose): one camera, constant points, CauchyLoss(1).
     Returns (extrinsic (3,4), intr_params (4,), summary).  COLMAP weights each residual by
-    loss only; covariance weighting is off."""
+    loss only; covariance weighting is off.  `options` / `loss` / `loss_scale`: another Options struct or loss than
+    RefineAbsolutePose's (tests/pose_cases.py); the defaults are what pycolmap runs."""
     sel = np.nonzero(np.asarray(inlier_mask, bool))[0]
     n = len(sel)
     cam_q = np.ascontiguousarray(rotmat_to_quat(extrinsic[None, :, :3]))
@@ -285,9 +286,9 @@ def pose_refinement(extrinsic, points2D, points3D, inlier_mask, intr_params, cam
     row_ptr = np.arange(n + 1, dtype=np.int32)
     obs_cam = np.zeros(n, np.int32)
     obs_uv = np.ascontiguousarray(np.asarray(points2D, np.float64)[sel])
-    opt = ceres_options(100, 1e-6, 1.0, 1e-8)      # Ceres defaults + COLMAP gradient_tolerance=1.0
+    opt = options or ceres_options(100, 1e-6, 1.0, 1e-8)      # Ceres defaults + COLMAP gradient_tolerance=1.0
     summary = solve_csr(cam_q, cam_t, intr, pts, np.zeros(1, np.int32), row_ptr, obs_cam, obs_uv, MODEL[camera_type],
-                        opt, refine_focal=refine_focal_length, refine_extra=refine_extra_params, loss=1,
-                        loss_scale=1.0, pt_const=np.ones(n, np.uint8))
+                        opt, refine_focal=refine_focal_length, refine_extra=refine_extra_params, loss=loss,
+                        loss_scale=loss_scale, pt_const=np.ones(n, np.uint8))
     ext = np.concatenate([quat_to_rotmat(cam_q)[0], cam_t[0][:, None]], -1)
     return ext, intr[0].copy(), summary

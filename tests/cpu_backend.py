@@ -50,12 +50,19 @@ def pose_refinement_batch(extrinsics, intr_params, points2D, points3D, inlier_ma
     ext, intr = _n(extrinsics).astype(np.float64).copy(), _n(intr_params).astype(np.float64).copy()
     p2, p3, mk, rf = _n(points2D), _n(points3D), _n(inlier_mask).astype(bool), _n(refine_flags)
     sums = []
+    from vggsfm_amd.ba_options import AbsolutePoseRefinementOptions
+    refopts = refopts or AbsolutePoseRefinementOptions()
+    # (vggsfm_amd.pose._options: Ceres defaults + the caller's gradient_tolerance / max_num_iterations)
+    o = OB.ceres_options(refopts.max_num_iterations, 1e-6, refopts.gradient_tolerance, 1e-8)
     for f in [int(i) for i in (frame_ids.tolist() if torch.is_tensor(frame_ids) else frame_ids)]:
         k = 4 if camera_type == "SIMPLE_RADIAL" else 3
         e, p, s = OB.pose_refinement(ext[f], p2[f], p3, mk[f], intr[f, :k], camera_type,
-                                     refine_focal_length=bool(rf[f] & 1), refine_extra_params=bool(rf[f] & 2))
+                                     refine_focal_length=bool(rf[f] & 1), refine_extra_params=bool(rf[f] & 2),
+                                     options=o, loss=LOSS["CAUCHY"], loss_scale=refopts.loss_function_scale)
         ext[f], intr[f, :k] = e, p[:k]
-        sums.append(dict(frame=f, **{key: s[key] for key in ("initial_cost", "final_cost", "num_iterations", "termination")}))
+        sums.append(dict(frame=f, **{key: s[key] for key in ("initial_cost", "final_cost", "num_iterations",
+                                                             "num_successful_steps", "num_unsuccessful_steps",
+                                                             "termination", "n_reduced")}))
     return _t(ext), _t(intr), sums
 
 

@@ -26,6 +26,7 @@ from tests import test_gpu_fundamental as TF
 from tests import test_gpu_geometry as TG
 from tests import test_gpu_p3p as TP
 from tests import test_gpu_pose as TPO
+from tests import test_gpu_pose_regimes as TPR
 from tests import test_gpu_reproj_video as TR
 from tests import test_gpu_triangulation as TT
 from tests.poison import equals_pattern, poisoned_allocations
@@ -200,6 +201,8 @@ CASES = {
     "p3p_plain": lambda mp: TP.test_p3p_ransac_matches_oracle_on_same_samples(5, 700, 256, 1),
     "p3p_groups": lambda mp: TP.test_p3p_ransac_matches_oracle_on_same_samples(6, 300, 64, 3),
     "pose_refine": lambda mp: TPO.test_pose_refinement_matches_oracle("SIMPLE_RADIAL", 3),
+    # 5 inliers of 800: 251 of the block's 256 lanes add nothing, so the block reduction is all there is to get wrong
+    "pose_refine_5_inliers": lambda mp: TPR.test_parity("n5_fk"),
     # dense depth: sparse depth, align, apply, unproject
     "dense_depth": lambda mp: (TDD.test_sparse_depth_matches_reference("radial_shared"),
                                TDD.test_align_replays_sklearn_draws("radial_shared"),

@@ -184,8 +184,10 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(
           mcc = -dg - 0.5 * dhd;
         }
         if (bad || !(mcc > 0.0)) {
+          // (the step that exhausts the streak ends the solve: it is not counted as an unsuccessful step -- Ceres leaves
+          //  HandleInvalidStep before the iteration is recorded, and so does the oracle)
           if (++invalid_streak >= opt.max_num_consecutive_invalid_steps) { done = 1; term = 5; }
-          radius /= decrease; decrease *= 2.0; step_ok = false; ++n_unsucc;
+          else { radius /= decrease; decrease *= 2.0; step_ok = false; ++n_unsucc; }
           sh_flag[1] = -1;                       // no candidate this round
         } else {
           invalid_streak = 0;

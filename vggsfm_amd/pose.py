@@ -62,7 +62,9 @@ def pose_refinement_batch(extrinsics, intr_params, points2D, points3D, inlier_ma
     for i in range(F):
         s = _lib.BASummary.from_buffer_copy(raw[i * ctypes.sizeof(_lib.BASummary):(i + 1) * ctypes.sizeof(_lib.BASummary)])
         sums.append(dict(frame=int(fid[i]), initial_cost=s.initial_cost, final_cost=s.final_cost,
-                         num_iterations=s.num_iterations, termination=s.termination))
+                         num_iterations=s.num_iterations, num_successful_steps=s.num_successful_steps,
+                         num_unsuccessful_steps=s.num_unsuccessful_steps, termination=s.termination,
+                         n_reduced=s.n_reduced))
     return out_ext, intr, sums
 
 
