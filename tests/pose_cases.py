@@ -353,10 +353,8 @@ def run_kernel(cam_q, cam_t, intr, tracks, points, mask, num_rows, P, frame_ids,
     summ = torch.zeros(max(F, 1) * size, dtype=torch.uint8, device="cuda")
     co = device_options(options)
     is64 = int(tracks is not None and tracks.dtype == torch.float64)
-    rc = L.vgg_pose_refine(_lib.ptr(points), _lib.ptr(tracks), is64, _lib.ptr(mask),
-                           int(num_rows), int(P), _lib.ptr(fid), F, _lib.ptr(cam_q), _lib.ptr(cam_t), _lib.ptr(intr),
-                           OB.MODEL[model], _lib.ptr(flags), ctypes.byref(co), int(loss), ctypes.c_double(scale),
-                           _lib.ptr(summ), _lib.stream_ptr())
+    rc = L.vgg_pose_refine(points, tracks, is64, mask, int(num_rows), int(P), fid, F, cam_q, cam_t, intr, OB.MODEL[model],
+                           flags, ctypes.byref(co), int(loss), scale, summ, _lib.stream_ptr())
     if check:
         _lib.check(rc, "vgg_pose_refine")
     raw = summ.cpu().numpy().tobytes()

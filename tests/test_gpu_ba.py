@@ -42,7 +42,7 @@ def test_cholesky_solve(n):
     Ad = np.tril(A) + np.triu(rng.normal(size=(n, n)), 1)
     At, bt = D(Ad), D(b)
     fail = torch.zeros(1, dtype=torch.int32, device="cuda")
-    rc = _lib.lib().vgg_cholesky_solve(_lib.ptr(At), _lib.ptr(bt), n, _lib.ptr(_chol_ws(n)), _lib.ptr(fail), _lib.stream_ptr())
+    rc = _lib.lib().vgg_cholesky_solve(At, bt, n, _chol_ws(n), fail, _lib.stream_ptr())
     assert rc == 0
     x = bt.cpu().numpy()
     assert int(fail.item()) == 0
@@ -62,7 +62,7 @@ def test_cholesky_solve_fused_rhs_row(n):
     buf = D(np.concatenate([np.tril(A).ravel(), b]))
     fail = torch.zeros(1, dtype=torch.int32, device="cuda")
     At, bt = buf[:n * n], buf[n * n:]
-    rc = _lib.lib().vgg_cholesky_solve(_lib.ptr(At), _lib.ptr(bt), n, _lib.ptr(_chol_ws(n)), _lib.ptr(fail), _lib.stream_ptr())
+    rc = _lib.lib().vgg_cholesky_solve(At, bt, n, _chol_ws(n), fail, _lib.stream_ptr())
     assert rc == 0 and int(fail.item()) == 0
     xr = np.linalg.solve(A, b)
     np.testing.assert_allclose(bt.cpu().numpy(), xr, rtol=1e-8, atol=1e-10 * np.abs(xr).max())
@@ -87,10 +87,9 @@ def test_cholesky_solve_split_matches_plain(n, sa, sb):
         fail = torch.zeros(1, dtype=torch.int32, device="cuda")
         At, bt = buf[:n * n], buf[n * n:]
         if split:
-            rc = _lib.lib().vgg_cholesky_solve_split(_lib.ptr(At), _lib.ptr(bt), n, sa, sb, _lib.ptr(_chol_ws(n)), _lib.ptr(fail),
-                                                     _lib.stream_ptr())
+            rc = _lib.lib().vgg_cholesky_solve_split(At, bt, n, sa, sb, _chol_ws(n), fail, _lib.stream_ptr())
         else:
-            rc = _lib.lib().vgg_cholesky_solve(_lib.ptr(At), _lib.ptr(bt), n, _lib.ptr(_chol_ws(n)), _lib.ptr(fail), _lib.stream_ptr())
+            rc = _lib.lib().vgg_cholesky_solve(At, bt, n, _chol_ws(n), fail, _lib.stream_ptr())
         assert rc == 0 and int(fail.item()) == 0
         out.append((np.tril(At.cpu().numpy().reshape(n, n)), bt.cpu().numpy()))
     xr = np.linalg.solve(A, b)
@@ -137,8 +136,7 @@ def test_cholesky_envelope_matches_lapack(n, band, arrow):
     fail = torch.zeros(1, dtype=torch.int32, device="cuda")
     At, bt = buf[:n * n], buf[n * n:]
     fb_dev, ws = D(first_blk), _chol_ws(n)           # (kept alive until the launches have run: the call is asynchronous)
-    rc = _lib.lib().vgg_cholesky_solve_envelope(_lib.ptr(At), _lib.ptr(bt), n, _lib.ptr(fb_dev), _lib.ptr(ws),
-                                                _lib.ptr(fail), _lib.stream_ptr())
+    rc = _lib.lib().vgg_cholesky_solve_envelope(At, bt, n, fb_dev, ws, fail, _lib.stream_ptr())
     assert rc == 0 and int(fail.item()) == 0
     xr = np.linalg.solve(Ap, b)
     np.testing.assert_allclose(bt.cpu().numpy(), xr, rtol=1e-8, atol=1e-10 * np.abs(xr).max())
@@ -316,7 +314,7 @@ def test_cholesky_flags_indefinite():
     A[17, 17] = -1.0
     At, bt = D(A), D(np.ones(40))
     fail = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _lib.lib().vgg_cholesky_solve(_lib.ptr(At), _lib.ptr(bt), 40, _lib.ptr(_chol_ws(40)), _lib.ptr(fail), _lib.stream_ptr())
+    _lib.lib().vgg_cholesky_solve(At, bt, 40, _chol_ws(40), fail, _lib.stream_ptr())
     torch.cuda.synchronize()
     assert int(fail.item()) == 1
 
@@ -348,8 +346,7 @@ def test_cholesky_single_launch_flags_bad_pivots(n, pos, kind):
         A[pos, pos] = A[pos - 1, pos - 1] - 1e-9
     buf = D(np.concatenate([np.tril(A).ravel(), rng.normal(size=n)]))
     fail = torch.zeros(1, dtype=torch.int32, device="cuda")
-    rc = _lib.lib().vgg_cholesky_solve(_lib.ptr(buf[:n * n]), _lib.ptr(buf[n * n:]), n, _lib.ptr(_chol_ws(n)), _lib.ptr(fail),
-                                       _lib.stream_ptr())
+    rc = _lib.lib().vgg_cholesky_solve(buf[:n * n], buf[n * n:], n, _chol_ws(n), fail, _lib.stream_ptr())
     torch.cuda.synchronize()
     assert rc == 0 and int(fail.item()) == 1, (n, pos, kind)
 

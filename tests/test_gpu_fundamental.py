@@ -2,7 +2,6 @@
 two mirror each other operation by operation (float64, no FMA contraction, fixed-order sums), so hypotheses, counts,
 winners and inlier masks must be identical -- plus the behaviour of ``estimate_preliminary_cameras`` on a synthetic
 sequence.  Parity with the reference's float32 / kornia implementation is unpinned (oracle/fundamental.py header)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -38,12 +37,10 @@ def test_seven_point_and_score_match_oracle_bitwise():
     d1, d2, ds, dm = D(x1), D(x2), D(smp), D(vm.astype(np.uint8))        # (kept alive across the raw-pointer calls)
     F7 = torch.empty((B, H, 3, 9), dtype=torch.float64, device="cuda")
     v7 = torch.empty((B, H, 3), dtype=torch.uint8, device="cuda")
-    _lib.check(L.vgg_fmat_seven_point(_lib.ptr(d1), _lib.ptr(d2), _lib.ptr(ds), B, N, H, _lib.ptr(F7), _lib.ptr(v7),
-                                      _lib.stream_ptr()), "seven")
+    _lib.check(L.vgg_fmat_seven_point(d1, d2, ds, B, N, H, F7, v7, _lib.stream_ptr()), "seven")
     cnt = torch.empty((B, 3 * H), dtype=torch.int32, device="cuda")
     rs = torch.empty((B, 3 * H), dtype=torch.float64, device="cuda")
-    _lib.check(L.vgg_fmat_score(_lib.ptr(d1), _lib.ptr(d2), _lib.ptr(dm), _lib.ptr(F7), _lib.ptr(v7), B, N,
-                                3 * H, ctypes.c_double(1.0), _lib.ptr(cnt), _lib.ptr(rs), _lib.stream_ptr()), "score")
+    _lib.check(L.vgg_fmat_score(d1, d2, dm, F7, v7, B, N, 3 * H, 1.0, cnt, rs, _lib.stream_ptr()), "score")
     for b in range(B):
         Fo, vo = Fd.seven_point(x1[b][smp], x2[b][smp])
         np.testing.assert_array_equal(v7[b].cpu().numpy().astype(bool), vo)

@@ -10,7 +10,6 @@ representative case of each entry -- the existing test itself, with its inputs a
   (d) no floating-point value read back is still the pattern (0xFF or 0x7F in every byte), nor any 32 / 64-bit integer
       0x7F7F... -- neither is a value the kernels produce.
 Then the contracts of the multi-GPU reduce buffers (include/vggsfm_amd.h, vgg_ba_begin .. vgg_ba_reduce_buffer)."""
-import ctypes
 import hashlib
 import os
 
@@ -273,12 +272,10 @@ def test_split_exchange_regions_fit_the_carve(W, S, shared, monkeypatch):
     prob = _split_problem(S, shared)
     s = ShardedBA(prob, prepare_ba_options())
     L = _lib.lib()
-    assert L.vgg_ba_phase(ctypes.byref(s.cp), ctypes.byref(s.co), _lib.ptr(s.ws), 12, _lib.stream_ptr()) == 0
-    p, cnt = ctypes.POINTER(ctypes.c_double)(), ctypes.c_size_t()
-    _lib.check(L.vgg_ba_reduce_buffer(ctypes.byref(s.cp), ctypes.byref(s.co), _lib.ptr(s.ws), 7, ctypes.byref(p),
-                                      ctypes.byref(cnt)), "vgg_ba_reduce_buffer")
-    M, a = s.bufs[4].numel(), int(cnt.value)
-    assert 0 < a < M and ctypes.addressof(p.contents) == s.bufs[4].data_ptr()
+    assert L.vgg_ba_phase(*s._abi, 12, _lib.stream_ptr()) == 0
+    address, a = _lib.reduce_buffer(*s._abi, 7)
+    M = s.bufs[4].numel()
+    assert 0 < a < M and address == s.bufs[4].data_ptr()
     ca, cb, c = -(-a // W), -(-(M - a) // W), -(-M // W)
     room4 = (s.bufs[5].data_ptr() - s.bufs[4].data_ptr()) // 8
     assert W * (ca + cb) <= room4, (W, W * (ca + cb) - M, room4 - M)

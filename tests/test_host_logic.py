@@ -3,6 +3,7 @@ C-ABI library's exports.  No compute kernel is called here."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -27,13 +28,57 @@ def T(x):
     return None if x is None else torch.from_numpy(np.ascontiguousarray(x))
 
 
+def _c_kind(decl):
+    """Kind of a C parameter or return declaration: "pointer", or the spelling of its value type."""
+    decl = " ".join(decl.split())
+    if "*" in decl:
+        return "pointer"
+    return next(k for k in ("unsigned long long", "size_t", "double", "long", "int") if re.match(rf"{k}\b", decl))
+
+
+def _parse_header(header):
+    """-> ({function: (return kind, [parameter kinds])}, {struct: [(field, ctypes type)]}) of include/vggsfm_amd.h."""
+    src = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)                  # comments
+    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)                      # preprocessor lines
+    field_type = {"int32_t": ctypes.c_int32, "double": ctypes.c_double}
+    structs = {}
+    for body, name in re.findall(r"typedef struct \{(.*?)\} (\w+);", src, flags=re.S):
+        fields = structs[name] = []
+        for stmt in filter(None, (" ".join(s.split()) for s in body.split(";"))):
+            ctype, names = re.fullmatch(r"(.*?[\s*]) ?(\w+(?:, \w+)*)", stmt).groups()
+            fields += [(n, ctypes.c_void_p if "*" in ctype else field_type[ctype.strip()]) for n in names.split(", ")]
+    src = re.sub(r"typedef struct \{.*?\} \w+;", " ", src, flags=re.S)
+    functions = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(vgg_\w+)\s*\(([^)]*)\)\s*;", src):
+        functions[name] = (_c_kind(ret), [_c_kind(p) for p in params.split(",") if p.strip() != "void"])
+    return functions, structs
+
+
 def test_library_loads_and_exports_every_declared_symbol():
+    """The binding's table and structs against the header, TYPE BY TYPE: per function the return type and the number and
+    kind of the parameters, per struct the fields in the header's order with the matching ctypes type; table, header and the
+    library's dynamic symbols name the same set.  (A ctypes binding with a wrong argument type fails silently otherwise.)"""
     assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
     L = ctypes.CDLL(_lib.LIB_PATH)
     header = open(os.path.join(ROOT, "include", "vggsfm_amd.h")).read()
-    declared = set(re.findall(r"\b(vgg_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.EXPORTED)
-    for sym in declared:
+    functions, structs = _parse_header(header)
+    assert len(functions) == 49 and sum(len(p) for _, p in functions.values()) > 400
+    restype_kind = {ctypes.c_char_p: "pointer", ctypes.c_int: "int", ctypes.c_size_t: "size_t"}
+    native = {ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_int: "int"}
+    table = {name: (restype_kind[res], [getattr(a, "kind", None) or native[a] for a in args])
+             for name, (res, args) in _lib.SIGNATURES.items()}
+    assert set(table) == set(functions) and _lib.EXPORTED == list(_lib.SIGNATURES)
+    for name in functions:
+        assert table[name] == functions[name], name
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    assert set(re.findall(r" T (vgg_\w+)$", nm, flags=re.M)) == set(functions)
+    binding = {"vgg_ba_problem": _lib.BAProblem, "vgg_ba_options": _lib.BAOptions, "vgg_ba_iteration": _lib.BAIteration,
+               "vgg_ba_summary": _lib.BASummary}
+    assert set(structs) == set(binding)
+    for name, st in binding.items():
+        assert list(st._fields_) == structs[name], name
+    assert len(structs["vgg_ba_problem"]) == 35
+    for sym in functions:
         assert hasattr(L, sym), sym
     L.vgg_build_arch.restype = ctypes.c_char_p
     assert L.vgg_build_arch() == b"gfx950"
@@ -43,6 +88,94 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert [int(L.vgg_abi_sizeof(i)) for i in range(5)] == [ctypes.sizeof(t) for t in (_lib.BAProblem, _lib.BAOptions,
                                                                                        _lib.BAIteration, _lib.BASummary)] + [0]
     assert _lib.lib() is not None
+
+
+def test_the_header_parser_reads_kinds_and_field_order():
+    """The comparison above is not vacuous: what the parser reads for a few declarations, pinned by hand (long / int /
+    size_t told apart, parameter counts, field order), and a binding with cam_q / cam_t swapped -- same sizeof -- differs."""
+    functions, structs = _parse_header(open(os.path.join(ROOT, "include", "vggsfm_amd.h")).read())
+    assert functions["vgg_reproj_stats"] == ("int", ["pointer", "pointer", "long", "int", "pointer", "pointer", "size_t",
+                                                     "pointer"])
+    assert functions["vgg_depth_align"][1][10] == "unsigned long long" and functions["vgg_build_arch"] == ("pointer", [])
+    assert functions["vgg_ba_tuning"] == ("int", ["int"] * 4) and functions["vgg_abi_sizeof"] == ("size_t", ["int"])
+    names = [n for n, _ in structs["vgg_ba_problem"]]
+    assert names.index("cam_q") + 1 == names.index("cam_t") and structs["vgg_ba_problem"][8] == ("loss_scale", ctypes.c_double)
+    assert structs["vgg_ba_summary"][:3] == [("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double),
+                                             ("num_iterations", ctypes.c_int32)]
+    swapped = list(_lib.BAProblem._fields_)
+    q = names.index("cam_q")
+    swapped[q], swapped[q + 1] = swapped[q + 1], swapped[q]
+    assert swapped != structs["vgg_ba_problem"] and list(_lib.BAProblem._fields_) == structs["vgg_ba_problem"]
+    wrong_row = list(functions["vgg_reproj_stats"][1])
+    wrong_row[2], wrong_row[3] = wrong_row[3], wrong_row[2]
+    assert wrong_row != [a.kind for a in _lib.SIGNATURES["vgg_reproj_stats"][1]]
+
+
+def test_64_bit_values_reach_the_library():
+    """Bare Python ints through the table: a long above 2^32 arrives whole (without argtypes ctypes passes a 32-bit int and
+    both calls of a pair return the same size)."""
+    L = _lib.lib()
+    for fn in (L.vgg_reproj_stats_workspace_bytes, L.vgg_depth_align_workspace_bytes):
+        small, big = fn(5), fn(2 ** 33 + 5)
+        assert big != small and big > 2 ** 33, (small, big)
+
+
+def test_out_of_range_arguments_are_refused_not_masked():
+    """A value that does not fit its C type raises ctypes.ArgumentError before the library is entered (so the entries that
+    need a GPU are safe to call here); bools, numpy integers and ctypes instances of the right type pass."""
+    L = _lib.lib()
+    with pytest.raises(ctypes.ArgumentError, match="does not fit the C type int"):
+        L.vgg_cholesky_workspace_bytes(2 ** 31)
+    try:
+        with pytest.raises(ctypes.ArgumentError, match="does not fit the C type int"):
+            L.vgg_ba_tuning(2 ** 32 + 8, 0, 0, 0)
+    finally:
+        assert L.vgg_ba_tuning(0, -1, 0, 0) == 0
+    with pytest.raises(ctypes.ArgumentError, match="does not fit the C type size_t"):
+        L.vgg_reproj_stats(None, None, 1, 0, None, None, -1, None)
+    with pytest.raises(ctypes.ArgumentError):
+        L.vgg_cholesky_workspace_bytes(1.5)
+    with pytest.raises(ctypes.ArgumentError):
+        L.vgg_cholesky_workspace_bytes(ctypes.c_double(3))
+    want = L.vgg_cholesky_workspace_bytes(3)
+    assert want > 0 and L.vgg_cholesky_workspace_bytes(True) == L.vgg_cholesky_workspace_bytes(1)
+    for three in (np.int64(3), ctypes.c_int(3), ctypes.c_long(3)):
+        assert L.vgg_cholesky_workspace_bytes(three) == want
+
+
+def test_pointer_parameters_take_tensors_none_and_ctypes_pointers():
+    """Both calling styles: a tensor as it is (its data_ptr(), host memory here) and the explicit wrappers."""
+    L = _lib.lib()
+    pb, op = _lib.BAProblem(), _lib.BAOptions()
+    pb.num_cams, pb.num_pts, pb.num_obs, pb.num_intr = 20, 10, 100, 1
+    pb.num_chunks, pb.num_tile_batches, pb.num_segments, pb.num_tiles = 4, 1, 8, 3
+    op.max_num_iterations = 5
+    ws = torch.zeros(64, dtype=torch.uint8)                         # (the carve-up only does address arithmetic)
+    address, count = _lib.reduce_buffer(ctypes.byref(pb), ctypes.byref(op), ws, 4)
+    wrapped_address, wrapped_count = ctypes.c_void_p(), ctypes.c_size_t()
+    assert L.vgg_ba_reduce_buffer(ctypes.byref(pb), ctypes.pointer(op), _lib.ptr(ws), ctypes.c_int(4),
+                                  ctypes.byref(wrapped_address), ctypes.byref(wrapped_count)) == 0
+    assert (wrapped_address.value, wrapped_count.value) == (address, count) and count > 0
+    assert address >= ws.data_ptr()
+    assert _lib.reduce_buffer(ctypes.byref(pb), ctypes.byref(op), (ctypes.c_char * 64)(), 4)[1] == count
+    with pytest.raises(ctypes.ArgumentError):
+        L.vgg_ba_reduce_buffer(ctypes.byref(pb), ctypes.byref(op), 1.5, 4, None, None)
+
+
+def test_no_call_site_declares_or_casts_c_types():
+    """Under vggsfm_amd/ only _lib.py sets .argtypes / .restype, and no scalar is wrapped inside the argument list of an
+    ``L.vgg_*`` call (out-parameter objects made on a line of their own are not calls' arguments)."""
+    cast = re.compile(r"\bc_(int|long|size_t|double|ulonglong)\(")
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "vggsfm_amd")):
+        for f in (f for f in files if f.endswith(".py") and f != "_lib.py"):
+            src = open(os.path.join(dirpath, f)).read()
+            assert ".argtypes" not in src and ".restype" not in src, f
+            for m in re.finditer(r"\.vgg_\w+\(", src):
+                depth, k = 1, m.end()
+                while depth:
+                    depth += (src[k] == "(") - (src[k] == ")")
+                    k += 1
+                assert not cast.search(src[m.end():k]), (f, src[m.start():k])
 
 
 def test_binding_rejects_a_library_with_another_abi(monkeypatch):
@@ -545,10 +678,8 @@ def test_split_exchange_partition_counts_from_the_c_abi():
         kd = rf + (1 if (rk and model == 1) else 0)
         n = 6 * C + kd * (1 if shared else C)
         fake = (ctypes.c_char * 64)()                               # (the carve-up only does address arithmetic)
-        cnt, ptr = ctypes.c_size_t(), ctypes.POINTER(ctypes.c_double)()
-        assert L.vgg_ba_reduce_buffer(ctypes.byref(pb), ctypes.byref(op), fake, 4, ctypes.byref(ptr), ctypes.byref(cnt)) == 0
-        assert cnt.value == n * (n + 1) // 2 + n
-        assert L.vgg_ba_reduce_buffer(ctypes.byref(pb), ctypes.byref(op), fake, 7, ctypes.byref(ptr), ctypes.byref(cnt)) == 0
+        assert _lib.reduce_buffer(ctypes.byref(pb), ctypes.byref(op), fake, 4)[1] == n * (n + 1) // 2 + n
+        count_a = _lib.reduce_buffer(ctypes.byref(pb), ctypes.byref(op), fake, 7)[1]
 
         def group(x):                                               # camera group of a reduced index; -1: shared-intrinsics border
             if x < 6 * C:
@@ -559,4 +690,4 @@ def test_split_exchange_partition_counts_from_the_c_abi():
         r, c = np.meshgrid(idx, idx, indexing="ij")
         lower = c <= r
         part_a = lower & (g[r] != g[c]) & (g[r] >= 0) & (g[c] >= 0)
-        assert cnt.value == int(part_a.sum()), (C, model, rf, rk, shared)
+        assert count_a == int(part_a.sum()), (C, model, rf, rk, shared)

@@ -3,8 +3,13 @@
 There is NO fallback: if the shared library is missing or was built for another target, importing
 a product function that needs it raises.  torch is imported first so that the library resolves
 ``libamdhip64.so.7`` to the HIP runtime torch already loaded (same streams, same allocations).
+
+The C type of every argument of every entry is declared once, in ``SIGNATURES`` below, and applied when the library is
+loaded: callers pass tensors, ``None``, ints and floats as they are.  A new C-ABI entry needs one prototype in the
+header and one row in that table (tests/test_host_logic.py compares the two, type by type).
 """
 import ctypes
+import operator
 import os
 
 import torch  # noqa: F401  (must be loaded before the HIP library, see module docstring)
@@ -57,18 +62,92 @@ class BASummary(ctypes.Structure):
                 ("n_reduced", ctypes.c_int32), ("num_log", ctypes.c_int32)]
 
 
-# every symbol include/vggsfm_amd.h declares (tests check the library exports all of them)
-EXPORTED = ["vgg_build_arch", "vgg_abi_version", "vgg_abi_sizeof", "vgg_project_points", "vgg_filter_points_workspace_bytes",
-            "vgg_filter_points", "vgg_cam_from_img_workspace_bytes", "vgg_cam_from_img",
-            "vgg_triangulate_workspace_bytes", "vgg_triangulate_tracks", "vgg_triangulate_by_pair", "vgg_triangulate_chunks_workspace_bytes",
-            "vgg_triangulate_tracks_chunks", "vgg_ba_workspace_bytes", "vgg_ba_solve",
-            "vgg_ba_begin", "vgg_ba_phase", "vgg_ba_reduce_buffer", "vgg_ba_finish", "vgg_cholesky_solve",
-            "vgg_ba_profile", "vgg_ba_profile_read", "vgg_cholesky_workspace_bytes", "vgg_pose_refine",
-            "vgg_p3p_ransac_workspace_bytes", "vgg_p3p_ransac", "vgg_fmat_seven_point", "vgg_fmat_score",
-            "vgg_fmat_eight_point", "vgg_fmat_residuals", "vgg_cholesky_solve_split", "vgg_ba_poll_done", "vgg_ba_tuning", "vgg_cholesky_solve_envelope", "vgg_ba_set_tile_rhs", "vgg_triangulate_tracks_chunks_enqueue",
-            "vgg_sparse_depth", "vgg_depth_align_workspace_bytes", "vgg_depth_align", "vgg_depth_apply", "vgg_depth_unproject",
-            "vgg_reproj_stats_workspace_bytes", "vgg_reproj_stats", "vgg_reproj_visible", "vgg_reproj_draw",
-            "vgg_color_gather", "vgg_color_reduce", "vgg_track_owner", "vgg_track_resolve"]
+class _P:
+    """A pointer parameter: None (NULL), a tensor (its data_ptr(): device or host memory, the entry decides) or whatever
+    ctypes passes as void* (c_void_p, byref(...), a ctypes array or pointer)."""
+    kind = "pointer"
+    ready = (type(None), ctypes.c_void_p, type(ctypes.byref(ctypes.c_int())))   # what ctypes passes as it is (the cheap exit)
+
+    @staticmethod
+    def from_param(v):
+        if type(v) in _P.ready:
+            return v
+        return ctypes.c_void_p(v.data_ptr()) if isinstance(v, torch.Tensor) else ctypes.c_void_p.from_param(v)
+
+
+def _integer(kind, ctype):
+    """An integer parameter of C type `kind`: anything with __index__ (int, bool, numpy integer) or a ctypes integer.  A
+    value that does not fit is refused (plain ctypes argtypes would mask it to the low bits), and so is a float."""
+    def from_param(v):
+        if isinstance(v, ctype):
+            return v
+        i = v if type(v) is int else operator.index(v.value if isinstance(v, ctypes._SimpleCData) else v)
+        c = ctype(i)
+        if c.value != i:                                    # (ctypes kept the low bits only)
+            raise OverflowError(f"{i} does not fit the C type {kind}")
+        return c
+    return type(kind, (), {"kind": kind, "from_param": staticmethod(from_param)})
+
+
+_I, _L, _Z, _U = (_integer(*kc) for kc in (("int", ctypes.c_int), ("long", ctypes.c_long), ("size_t", ctypes.c_size_t),
+                                            ("unsigned long long", ctypes.c_ulonglong)))
+_D, _INT, _SIZE = ctypes.c_double, ctypes.c_int, ctypes.c_size_t
+
+# name -> (return type, parameter types) of every function include/vggsfm_amd.h declares, in the header's order.
+# vgg_ba_phase, called four to eight times per LM iteration, has ctypes' own types: converted in C, at the price that its
+# caller wraps the workspace (_lib.ptr) and that an out-of-range phase number would be masked, not refused.
+SIGNATURES = {
+    "vgg_build_arch": (ctypes.c_char_p, []),
+    "vgg_abi_version": (_INT, []),
+    "vgg_abi_sizeof": (_SIZE, [_I]),
+    "vgg_project_points": (_INT, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "vgg_filter_points_workspace_bytes": (_SIZE, [_I]),
+    "vgg_filter_points": (_INT, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _D, _D, _I, _D, _D, _P, _P, _P, _P]),
+    "vgg_cam_from_img_workspace_bytes": (_SIZE, [_I, _I, _I]),
+    "vgg_cam_from_img": (_INT, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _D, _D, _D, _P, _P, _P]),
+    "vgg_triangulate_chunks_workspace_bytes": (_SIZE, [_I, _I]),
+    "vgg_triangulate_tracks_chunks": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P]),
+    "vgg_triangulate_tracks_chunks_enqueue": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
+    "vgg_triangulate_by_pair": (_INT, [_P, _P, _I, _I, _P, _P]),
+    "vgg_triangulate_workspace_bytes": (_SIZE, [_I, _I, _I, _I]),
+    "vgg_triangulate_tracks": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P]),
+    "vgg_ba_workspace_bytes": (_SIZE, [_P, _P]),
+    "vgg_ba_solve": (_INT, [_P, _P, _P, _Z, _P, _P, _I, _P]),
+    "vgg_ba_begin": (_INT, [_P, _P, _P, _Z, _I, _I, _P]),
+    "vgg_ba_phase": (_INT, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "vgg_ba_reduce_buffer": (_INT, [_P, _P, _P, _I, _P, _P]),
+    "vgg_ba_finish": (_INT, [_P, _P, _P, _P, _P, _I, _P]),
+    "vgg_ba_poll_done": (_INT, [_P, _P, _P, _P, _P]),
+    "vgg_pose_refine": (_INT, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _D, _P, _P]),
+    "vgg_p3p_ransac_workspace_bytes": (_SIZE, [_I, _I]),
+    "vgg_p3p_ransac": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vgg_fmat_seven_point": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "vgg_fmat_score": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _P]),
+    "vgg_fmat_eight_point": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P]),
+    "vgg_fmat_residuals": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "vgg_ba_tuning": (_INT, [_I, _I, _I, _I]),
+    "vgg_ba_set_tile_rhs": (_INT, [_I]),
+    "vgg_ba_profile": (_INT, [_I, _I]),
+    "vgg_ba_profile_read": (_INT, [_I, _P, _P, _I]),
+    "vgg_cholesky_workspace_bytes": (_SIZE, [_I]),
+    "vgg_cholesky_solve": (_INT, [_P, _P, _I, _P, _P, _P]),
+    "vgg_cholesky_solve_split": (_INT, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "vgg_cholesky_solve_envelope": (_INT, [_P, _P, _I, _P, _P, _P, _P]),
+    "vgg_sparse_depth": (_INT, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P]),
+    "vgg_depth_align_workspace_bytes": (_SIZE, [_L]),
+    "vgg_depth_align": (_INT, [_P, _P, _P, _P, _P, _P, _I, _L, _P, _I, _U, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "vgg_depth_apply": (_INT, [_P, _P, _P, _P, _P, _I, _L, _P, _P, _P]),
+    "vgg_depth_unproject": (_INT, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "vgg_reproj_stats_workspace_bytes": (_SIZE, [_L]),
+    "vgg_reproj_stats": (_INT, [_P, _P, _L, _I, _P, _P, _Z, _P]),
+    "vgg_reproj_visible": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vgg_reproj_draw": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vgg_color_gather": (_INT, [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P, _P, _P]),
+    "vgg_color_reduce": (_INT, [_P, _L, _L, _P, _P, _P, _P, _P]),
+    "vgg_track_owner": (_INT, [_P, _I, _P, _I, _I, _I, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
+    "vgg_track_resolve": (_INT, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+}
+EXPORTED = list(SIGNATURES)
 
 _lib = None
 
@@ -88,12 +167,6 @@ def lib():
     arch = L.vgg_build_arch().decode()
     if arch != "gfx950":
         raise RuntimeError(f"libvggsfm_amd.so was built for {arch}, expected gfx950")
-    for name in ("vgg_filter_points_workspace_bytes", "vgg_cam_from_img_workspace_bytes",
-                 "vgg_triangulate_workspace_bytes", "vgg_triangulate_chunks_workspace_bytes", "vgg_ba_workspace_bytes",
-                 "vgg_cholesky_workspace_bytes", "vgg_p3p_ransac_workspace_bytes", "vgg_depth_align_workspace_bytes",
-                 "vgg_reproj_stats_workspace_bytes"):
-        getattr(L, name).restype = ctypes.c_size_t
-    L.vgg_ba_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     # a stale or variant build (VGGSFM_AMD_LIB) with another struct layout would be driven with shifted pointers: refuse it
     if not hasattr(L, "vgg_abi_sizeof") or L.vgg_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {L.vgg_abi_version()} but this binding speaks {ABI_VERSION}; rebuild "
@@ -103,6 +176,9 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -114,9 +190,16 @@ def check(rc, what):
 
 def ptr(t):
     """Device (or host) address of a tensor as void*; None -> NULL."""
-    if t is None:
-        return ctypes.c_void_p(0)
-    return ctypes.c_void_p(t.data_ptr())
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def reduce_buffer(problem, options, workspace, which):
+    """(device address, number of doubles) of reduce buffer `which` of a BA workspace (vgg_ba_reduce_buffer); `problem` and
+    `options` by reference, as the entry takes them."""
+    address, count = ctypes.c_void_p(), ctypes.c_size_t()
+    check(lib().vgg_ba_reduce_buffer(problem, options, workspace, which, ctypes.byref(address), ctypes.byref(count)),
+          "vgg_ba_reduce_buffer")
+    return address.value or 0, count.value
 
 
 def stream_ptr():

@@ -910,15 +910,14 @@ def solve(problem: DeviceProblem, options: Optional[BundleAdjustmentOptions] = N
     problem.loss_scale = options.loss_function_scale
     cp = problem.c_struct()
     co = _c_options(options)
-    nbytes = int(L.vgg_ba_workspace_bytes(ctypes.byref(cp), ctypes.byref(co)))
+    nbytes = L.vgg_ba_workspace_bytes(ctypes.byref(cp), ctypes.byref(co))
     if workspace is None or workspace.numel() < nbytes:
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=problem.pts.device)
     summ = _lib.BASummary()
     cap = options.solver_options.max_num_iterations + 2
     log = (_lib.BAIteration * cap)()
-    rc = L.vgg_ba_solve(ctypes.byref(cp), ctypes.byref(co), _lib.ptr(workspace), ctypes.c_size_t(workspace.numel()),
-                        ctypes.byref(summ), log, cap, _lib.stream_ptr())
-    _lib.check(rc, "vgg_ba_solve")
+    _lib.check(L.vgg_ba_solve(ctypes.byref(cp), ctypes.byref(co), workspace, workspace.numel(), ctypes.byref(summ), log, cap,
+                              _lib.stream_ptr()), "vgg_ba_solve")
     out = _summary_dict(summ, log, summ.num_log)
     if options.print_summary:
         print(f"Bundle adjustment report: residuals {problem.num_obs * 2}, parameters reduced {summ.n_reduced}, "

@@ -12,13 +12,13 @@ vggsfm/utils/utils.py:635-770) over ``vgg_sparse_depth`` / ``vgg_depth_align`` /
 
 Disparity maps are float32, as the depth model writes them.  There is no CPU path.
 """
-import ctypes
 from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from .reproj_video import _dev, _to_dev
 
 ALIGN_STATUS = {0: "ok", 1: "no observation", 2: "ill-posed", 3: "no consensus set", 4: "fewer than 2 usable points",
                 5: "recorded draws exhausted", 6: "recorded draw out of range"}
@@ -27,13 +27,6 @@ MAX_TRIALS = 20000
 SparseDepth = namedtuple("SparseDepth", "names obs_ptr uvd xyzid")
 Packed = namedtuple("Packed", "flat off heights widths max_pixels")
 AlignResult = namedtuple("AlignResult", "scale shift n_trials n_inliers n_kept status kept inlier")
-
-_c_long = ctypes.c_long
-_c_size = ctypes.c_size_t
-
-
-def _dev(device):
-    return torch.device("cuda" if device is None else device)
 
 
 def _camera_rows(reconstruction, image_ids):
@@ -81,11 +74,10 @@ def sparse_depth(reconstruction, device=None):
     xyzid = torch.empty((O, 4), dtype=torch.float64, device=dev)
     if O:
         pose, cam = _camera_rows(reconstruction, image_ids)
-        T = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        xyz = T(reconstruction._xyz[:reconstruction._n], np.float64)
-        args = (T(prow, np.int32), T(slot, np.int32), T(pid, np.int64), T(pose, np.float64), T(cam, np.float64))
-        _lib.check(L.vgg_sparse_depth(_lib.ptr(xyz), *[_lib.ptr(a) for a in args], _c_long(O), _lib.ptr(uvd),
-                                      _lib.ptr(xyzid), _lib.stream_ptr()), "vgg_sparse_depth")
+        args = ((reconstruction._xyz[:reconstruction._n], np.float64), (prow, np.int32), (slot, np.int32), (pid, np.int64),
+                (pose, np.float64), (cam, np.float64))
+        _lib.check(L.vgg_sparse_depth(*[_to_dev(a, dt, dev) for a, dt in args], O, uvd, xyzid, _lib.stream_ptr()),
+                   "vgg_sparse_depth")
     return SparseDepth(names, obs_ptr, uvd, xyzid)
 
 
@@ -150,17 +142,14 @@ def align(packed, uvd, obs_ptr, samples=None, seed=0, max_trials=MAX_TRIALS):
         d = samples if isinstance(samples, np.ndarray) and samples.ndim == 3 else pack_samples(samples, S)
         if d.shape[0] != S or d.shape[2] != 2:
             raise ValueError(f"samples must be (num_images={S}, T, 2), got {d.shape}")
-        draws = torch.from_numpy(np.ascontiguousarray(d, dtype=np.int32)).to(dev)
+        draws = _to_dev(d, np.int32, dev)
         T = d.shape[1]
-    ptr_t = torch.from_numpy(np.ascontiguousarray(obs_ptr, dtype=np.int64)).to(dev)
-    L.vgg_depth_align_workspace_bytes.argtypes = [_c_long]
-    nbytes = int(L.vgg_depth_align_workspace_bytes(_c_long(O)))
+    ptr_t = _to_dev(obs_ptr, np.int64, dev)
+    nbytes = L.vgg_depth_align_workspace_bytes(O)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    p = _lib.ptr
-    _lib.check(L.vgg_depth_align(p(packed.flat), p(packed.off), p(packed.heights), p(packed.widths), p(uvd), p(ptr_t),
-                                 ctypes.c_int(S), _c_long(O), p(draws), ctypes.c_int(T),
-                                 ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), ctypes.c_int(int(min(max_trials, 2 ** 31 - 1))),
-                                 *[p(t) for t in res], p(ws), _c_size(nbytes), _lib.stream_ptr()), "vgg_depth_align")
+    _lib.check(L.vgg_depth_align(packed.flat, packed.off, packed.heights, packed.widths, uvd, ptr_t, S, O, draws, T,
+                                 int(seed) & (2 ** 64 - 1), int(min(max_trials, 2 ** 31 - 1)), *res, ws, nbytes,
+                                 _lib.stream_ptr()), "vgg_depth_align")
     return res
 
 
@@ -170,10 +159,8 @@ def apply(packed, scale, shift, num_images=None):
     S = packed.off.numel() - 1 if num_images is None else int(num_images)
     depth = torch.zeros_like(packed.flat)
     if S > 0:
-        p = _lib.ptr
-        _lib.check(L.vgg_depth_apply(p(packed.flat), p(depth), p(packed.off), p(packed.heights), p(packed.widths),
-                                     ctypes.c_int(S), _c_long(packed.max_pixels), p(scale), p(shift), _lib.stream_ptr()),
-                   "vgg_depth_apply")
+        _lib.check(L.vgg_depth_apply(packed.flat, depth, packed.off, packed.heights, packed.widths, S, packed.max_pixels,
+                                     scale, shift, _lib.stream_ptr()), "vgg_depth_apply")
     return depth
 
 
@@ -191,11 +178,9 @@ def unproject(packed, depth, cam, inv_pose, num_images=None):
     N = pix.numel()
     xyz = torch.empty((N, 3), dtype=torch.float64, device=dev)
     if N:
-        T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        cam_t, inv_t = T(cam), T(inv_pose)
-        p = _lib.ptr
-        _lib.check(L.vgg_depth_unproject(p(local), p(img), _c_long(N), p(depth), p(packed.off), p(packed.widths), p(cam_t),
-                                         p(inv_t), p(xyz), _lib.stream_ptr()), "vgg_depth_unproject")
+        cam_t, inv_t = _to_dev(cam, np.float64, dev), _to_dev(inv_pose, np.float64, dev)
+        _lib.check(L.vgg_depth_unproject(local, img, N, depth, packed.off, packed.widths, cam_t, inv_t, xyz,
+                                         _lib.stream_ptr()), "vgg_depth_unproject")
     return xyz, counts
 
 

@@ -273,17 +273,15 @@ class ShardedBA:
         self.rank, self.world = rank, world_size
         self.cp = problem.c_struct()
         self.co = BA._c_options(self.options, overlap=(world_size == 1))
-        nbytes = int(self.L.vgg_ba_workspace_bytes(ctypes.byref(self.cp), ctypes.byref(self.co)))
-        self.nbytes = nbytes
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=problem.pts.device)
+        self.nbytes = self.L.vgg_ba_workspace_bytes(ctypes.byref(self.cp), ctypes.byref(self.co))
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=problem.pts.device)
+        # the leading arguments of every phase entry (cp, co and ws are only ever changed in place: rebuild this with them)
+        self._abi = (ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws))
         self.bufs = []
         for which in range(7):
-            p = ctypes.POINTER(ctypes.c_double)()
-            cnt = ctypes.c_size_t()
-            _lib.check(self.L.vgg_ba_reduce_buffer(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws), which,
-                                                   ctypes.byref(p), ctypes.byref(cnt)), "vgg_ba_reduce_buffer")
-            off = ctypes.addressof(p.contents) - self.ws.data_ptr()
-            self.bufs.append(self.ws[off:off + 8 * cnt.value].view(torch.float64))
+            address, count = _lib.reduce_buffer(*self._abi, which)
+            off = address - self.ws.data_ptr()
+            self.bufs.append(self.ws[off:off + 8 * count].view(torch.float64))
         if collectives is None and world_size > 1:
             collectives = _FunctionCollectives(all_reduce) if all_reduce is not None else Collectives(world_size)
         # collectives handed in explicitly are used at world size 1 as well: a one-rank RCCL communicator runs the whole
@@ -302,14 +300,9 @@ class ShardedBA:
         want_split = SPLIT_EXCHANGE if split_exchange is None else bool(split_exchange)
         self._split = False
         if want_split and (self._in_place or split_exchange == "emulated"):
-            rc = self.L.vgg_ba_phase(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws), 12, _lib.stream_ptr())
-            if rc == 0:
-                p = ctypes.POINTER(ctypes.c_double)()
-                cnt = ctypes.c_size_t()
-                _lib.check(self.L.vgg_ba_reduce_buffer(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws), 7,
-                                                       ctypes.byref(p), ctypes.byref(cnt)), "vgg_ba_reduce_buffer")
+            if self.L.vgg_ba_phase(*self._abi, 12, _lib.stream_ptr()) == 0:
                 W = max(world_size, 1)
-                a = int(cnt.value)
+                a = _lib.reduce_buffer(*self._abi, 7)[1]
                 ca, cb = -(-a // W), -(-(M - a) // W)
                 off5 = self.bufs[5].data_ptr() - self.ws.data_ptr()
                 # the split regions must fit the carve: buffer 4's up to buffer 5, buffer 6's within its count
@@ -322,12 +315,10 @@ class ShardedBA:
                 self._split = True
 
     def begin(self):
-        _lib.check(self.L.vgg_ba_begin(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws),
-                                       ctypes.c_size_t(self.nbytes), self.rank, self.world, _lib.stream_ptr()), "vgg_ba_begin")
+        _lib.check(self.L.vgg_ba_begin(*self._abi, self.nbytes, self.rank, self.world, _lib.stream_ptr()), "vgg_ba_begin")
 
     def _phase(self, i):
-        _lib.check(self.L.vgg_ba_phase(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws), i,
-                                       _lib.stream_ptr()), "vgg_ba_phase")
+        _lib.check(self.L.vgg_ba_phase(*self._abi, i, _lib.stream_ptr()), "vgg_ba_phase")
 
     def iteration(self):
         co = self.coll
@@ -366,8 +357,8 @@ class ShardedBA:
     def finish(self, log_cap=0):
         summ = _lib.BASummary()
         log = (_lib.BAIteration * max(log_cap, 1))()
-        _lib.check(self.L.vgg_ba_finish(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws), ctypes.byref(summ),
-                                        log if log_cap else None, log_cap, _lib.stream_ptr()), "vgg_ba_finish")
+        _lib.check(self.L.vgg_ba_finish(*self._abi, ctypes.byref(summ), log if log_cap else None, log_cap, _lib.stream_ptr()),
+                   "vgg_ba_finish")
         return BA._summary_dict(summ, log, summ.num_log if log_cap else 0)
 
     POLL = 8
@@ -375,8 +366,7 @@ class ShardedBA:
     def done(self):
         """Has the device-side control flow ended the solve?  (4-byte copy + stream synchronisation.)"""
         flag = ctypes.c_int32(0)
-        _lib.check(self.L.vgg_ba_poll_done(ctypes.byref(self.cp), ctypes.byref(self.co), _lib.ptr(self.ws), ctypes.byref(flag),
-                                           _lib.stream_ptr()), "vgg_ba_poll_done")
+        _lib.check(self.L.vgg_ba_poll_done(*self._abi, ctypes.byref(flag), _lib.stream_ptr()), "vgg_ba_poll_done")
         return bool(flag.value)
 
     def solve(self):

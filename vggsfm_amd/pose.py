@@ -48,10 +48,9 @@ def pose_refinement_batch(extrinsics, intr_params, points2D, points3D, inlier_ma
     rf = refine_flags.to(device=dev, dtype=torch.uint8).contiguous()
     summ = torch.zeros(F * ctypes.sizeof(_lib.BASummary), dtype=torch.uint8, device=dev)
     co = _options(refopts)
-    _lib.check(L.vgg_pose_refine(_lib.ptr(pts), _lib.ptr(tr), is64, _lib.ptr(mk), S, P, _lib.ptr(fid), F,
-                                 _lib.ptr(cam_q), _lib.ptr(cam_t), _lib.ptr(intr), MODEL_ID[camera_type], _lib.ptr(rf),
-                                 ctypes.byref(co), LOSS_ID["CAUCHY"], ctypes.c_double(refopts.loss_function_scale),
-                                 _lib.ptr(summ), _lib.stream_ptr()), "vgg_pose_refine")
+    _lib.check(L.vgg_pose_refine(pts, tr, is64, mk, S, P, fid, F, cam_q, cam_t, intr, MODEL_ID[camera_type], rf,
+                                 ctypes.byref(co), LOSS_ID["CAUCHY"], refopts.loss_function_scale, summ, _lib.stream_ptr()),
+               "vgg_pose_refine")
     out_ext = torch.cat([quat_to_rotmat(cam_q), cam_t[:, :, None]], -1)
     # frames that were not refined keep their exact input matrices
     keep = torch.ones(S, dtype=torch.bool, device=dev)
@@ -128,10 +127,9 @@ def p3p_ransac(points2D_normalized, points3D, candidate_mask, samples, max_error
     inl = torch.zeros((F, P), dtype=torch.uint8, device=dev)
     if F == 0:
         return pose, num, rsum, best, inl.bool()
-    ws = torch.empty(int(L.vgg_p3p_ransac_workspace_bytes(F, H)), dtype=torch.uint8, device=dev)
-    _lib.check(L.vgg_p3p_ransac(_lib.ptr(x), _lib.ptr(X), _lib.ptr(mk), _lib.ptr(smp), F, frames_per_sample_set, P, H,
-                                _lib.ptr(thr), _lib.ptr(pose), _lib.ptr(num), _lib.ptr(rsum), _lib.ptr(best), _lib.ptr(inl),
-                                _lib.ptr(ws), _lib.stream_ptr()), "vgg_p3p_ransac")
+    ws = torch.empty(L.vgg_p3p_ransac_workspace_bytes(F, H), dtype=torch.uint8, device=dev)
+    _lib.check(L.vgg_p3p_ransac(x, X, mk, smp, F, frames_per_sample_set, P, H, thr, pose, num, rsum, best, inl, ws,
+                                _lib.stream_ptr()), "vgg_p3p_ransac")
     return pose, num, rsum, best, inl.bool()
 
 

@@ -11,7 +11,6 @@ Circles follow an integer raster rule (4 x 4 sub-samples per pixel, DESIGN.md se
 anti-aliased fill; everything else -- statistics, centres, colours, the visible set and the drawing order -- is the
 reference's exactly.  There is no CPU path.
 """
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -25,12 +24,15 @@ MAX_GRID_CELLS = 1 << 25        # cells of one chunk of visibility grids (12 B e
 FILTER_MAX_CELLS = 1 << 27      # bounding-box cells of the standalone mask (filter_mask)
 
 Debug = namedtuple("Debug", "names obs_range visible centers colors stats")
-_c_long = ctypes.c_long
-_c_int = ctypes.c_int
 
 
 def _dev(device):
     return torch.device("cuda" if device is None else device)
+
+
+def _to_dev(a, dtype, dev):
+    """A host array as a contiguous device tensor of `dtype` (a numpy dtype)."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
 
 
 def colormap_lut(cmap):
@@ -81,12 +83,10 @@ def stats(points3D, point_ids, color_mode, device=None):
     if P == 0:
         raise ValueError("the reconstruction has no 3D points: the colour statistics are undefined")
     out = torch.zeros(8, dtype=torch.float64, device=dev)
-    L.vgg_reproj_stats_workspace_bytes.argtypes = [_c_long]
-    nbytes = int(L.vgg_reproj_stats_workspace_bytes(_c_long(P)))
+    nbytes = L.vgg_reproj_stats_workspace_bytes(P)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    p = _lib.ptr
-    _lib.check(L.vgg_reproj_stats(p(xyz if mode != 2 else None), p(ids if mode == 2 else None), _c_long(P), _c_int(mode),
-                                  p(out), p(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr()), "vgg_reproj_stats")
+    _lib.check(L.vgg_reproj_stats(xyz if mode != 2 else None, ids if mode == 2 else None, P, mode, out, ws, nbytes,
+                                  _lib.stream_ptr()), "vgg_reproj_stats")
     return out
 
 
@@ -158,7 +158,7 @@ def render(sparse_depth_device, points3D, point_ids, images, video_size, draw_ra
     img_sizes = hw[:, 0] * hw[:, 1] * 3
     img_off = np.concatenate([[0], np.cumsum(img_sizes)]).astype(np.int64)
 
-    T = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    T = lambda a, dt: _to_dev(a, dt, dev)
     st = stats(points3D, point_ids, color_mode, dev)
     flat = torch.cat([torch.as_tensor(images[n]).to(dev).reshape(-1) for n in names]) if S else \
         torch.zeros(0, dtype=torch.uint8, device=dev)
@@ -176,15 +176,12 @@ def render(sparse_depth_device, points3D, point_ids, images, video_size, draw_ra
         raise ValueError(f"a frame of {max_cells} grid cells is too large (at most 2^31 - 1)")
     grid_key = torch.empty(max_cells, dtype=torch.int64, device=dev)
     grid_obs = torch.empty(max_cells, dtype=torch.int32, device=dev)
-    p = _lib.ptr
     for b, e in chunks:
-        chunk_cells = int(grid_off[e] - grid_off[b])
-        _lib.check(L.vgg_reproj_visible(p(sd.uvd), p(sd.xyzid), p(range_t), p(h_t), p(w_t), p(goff_t), _c_int(b), _c_int(e),
-                                        _c_long(int(counts[b:e].max())), _c_long(chunk_cells), _c_int(r), _c_int(mode),
-                                        p(st), p(lut_t), _c_int(N), p(obs_cell), p(color), p(centers), p(visible),
-                                        p(grid_key), p(grid_obs), _lib.stream_ptr()), "vgg_reproj_visible")
-        _lib.check(L.vgg_reproj_draw(p(flat), p(ioff_t), p(h_t), p(w_t), p(goff_t), _c_int(b), _c_int(e), _c_int(H), _c_int(W),
-                                     _c_int(r), p(grid_obs), p(color), p(out[b:e]), _lib.stream_ptr()), "vgg_reproj_draw")
+        _lib.check(L.vgg_reproj_visible(sd.uvd, sd.xyzid, range_t, h_t, w_t, goff_t, b, e, counts[b:e].max(),
+                                        grid_off[e] - grid_off[b], r, mode, st, lut_t, N, obs_cell, color, centers, visible,
+                                        grid_key, grid_obs, _lib.stream_ptr()), "vgg_reproj_visible")
+        _lib.check(L.vgg_reproj_draw(flat, ioff_t, h_t, w_t, goff_t, b, e, H, W, r, grid_obs, color, out[b:e],
+                                     _lib.stream_ptr()), "vgg_reproj_draw")
     if not return_debug:
         return out
     c = color[:O].to(torch.int64)
@@ -222,16 +219,13 @@ def filter_mask(uvs_int, depths, max_cells=FILTER_MAX_CELLS):
                          f"{max_cells} the device grid supports")
     uvd = torch.stack([(uv[:, 0] - lo[0]).double(), (uv[:, 1] - lo[1]).double(), d.double()], dim=1).contiguous()
     L = _lib.lib()
-    T = lambda a, dt: torch.from_numpy(np.asarray(a, dtype=dt)).to(dev)
+    T = lambda a, dt: _to_dev(a, dt, dev)
     obs_cell = torch.empty(n, dtype=torch.int32, device=dev)
     visible = torch.empty(n, dtype=torch.uint8, device=dev)
     grid_key = torch.empty(w * h, dtype=torch.int64, device=dev)
     grid_obs = torch.empty(w * h, dtype=torch.int32, device=dev)
     rng, h_t, w_t, goff = T([[0, n]], np.int64), T([h], np.int32), T([w], np.int32), T([0, w * h], np.int64)
-    p = _lib.ptr
-    _lib.check(L.vgg_reproj_visible(p(uvd), None, p(rng), p(h_t), p(w_t), p(goff), _c_int(0), _c_int(1), _c_long(n),
-                                    _c_long(w * h), _c_int(0),
-                                    _c_int(0), None, None, _c_int(0), p(obs_cell), None, None, p(visible), p(grid_key),
-                                    p(grid_obs), _lib.stream_ptr()), "vgg_reproj_visible")
+    _lib.check(L.vgg_reproj_visible(uvd, None, rng, h_t, w_t, goff, 0, 1, n, w * h, 0, 0, None, None, 0, obs_cell, None, None,
+                                    visible, grid_key, grid_obs, _lib.stream_ptr()), "vgg_reproj_visible")
     m = visible.bool()
     return m if on_device else m.cpu().numpy()

@@ -2,7 +2,6 @@
 8-point local optimisation, winner by (inlier count, mean inlier residual) -- every image pair of the batch at once.
 Host side of ``vgg_fmat_seven_point`` / ``vgg_fmat_score`` / ``vgg_fmat_eight_point`` / ``vgg_fmat_residuals``; the
 only host-side step between the launches is the stable sort that selects the lo_num best hypotheses."""
-import ctypes
 
 import torch
 
@@ -17,8 +16,7 @@ def _score(L, p1, p2, vm, F, fvalid, thr):
     K = F.shape[1]
     cnt = torch.empty((B, K), dtype=torch.int32, device=p1.device)
     rs = torch.empty((B, K), dtype=torch.float64, device=p1.device)
-    _lib.check(L.vgg_fmat_score(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(vm), _lib.ptr(F), _lib.ptr(fvalid), B, N, K,
-                                ctypes.c_double(thr), _lib.ptr(cnt), _lib.ptr(rs), _lib.stream_ptr()), "vgg_fmat_score")
+    _lib.check(L.vgg_fmat_score(p1, p2, vm, F, fvalid, B, N, K, thr, cnt, rs, _lib.stream_ptr()), "vgg_fmat_score")
     return cnt, rs
 
 
@@ -29,8 +27,7 @@ def _eight_point(L, p1, p2, vm, Fsrc, cnt_src, lo, thr):
     order = torch.sort(cnt_src, dim=1, descending=True, stable=True).indices[:, :lo].to(torch.int32).contiguous()
     F = torch.empty((B, lo, 9), dtype=torch.float64, device=p1.device)
     ok = torch.empty((B, lo), dtype=torch.uint8, device=p1.device)
-    _lib.check(L.vgg_fmat_eight_point(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(vm), _lib.ptr(Fsrc), _lib.ptr(cnt_src), _lib.ptr(order),
-                                      B, N, K, lo, ctypes.c_double(thr), _lib.ptr(F), _lib.ptr(ok), _lib.stream_ptr()),
+    _lib.check(L.vgg_fmat_eight_point(p1, p2, vm, Fsrc, cnt_src, order, B, N, K, lo, thr, F, ok, _lib.stream_ptr()),
                "vgg_fmat_eight_point")
     return F, ok
 
@@ -59,8 +56,7 @@ def estimate_fundamental(points1, points2, max_ransac_iters=4096, max_error=1, l
     H = int(smp.shape[0])
     F7 = torch.empty((B, H, 3, 9), dtype=torch.float64, device=dev)
     v7 = torch.empty((B, H, 3), dtype=torch.uint8, device=dev)
-    _lib.check(L.vgg_fmat_seven_point(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(smp), B, N, H, _lib.ptr(F7), _lib.ptr(v7),
-                                      _lib.stream_ptr()), "vgg_fmat_seven_point")
+    _lib.check(L.vgg_fmat_seven_point(p1, p2, smp, B, N, H, F7, v7, _lib.stream_ptr()), "vgg_fmat_seven_point")
     Fa, va = F7.reshape(B, 3 * H, 9), v7.reshape(B, 3 * H)
     cnt, rs = _score(L, p1, p2, vm, Fa, va, thr)
     F8, v8 = _eight_point(L, p1, p2, vm, Fa, cnt, lo_num, thr)
@@ -85,8 +81,7 @@ def estimate_fundamental(points1, points2, max_ransac_iters=4096, max_error=1, l
     ar = torch.arange(B, device=dev)
     Fb = Fall[ar, best].contiguous()
     res = torch.empty((B, N), dtype=torch.float64, device=dev)
-    _lib.check(L.vgg_fmat_residuals(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(vm), _lib.ptr(Fb), B, N, _lib.ptr(res),
-                                    _lib.stream_ptr()), "vgg_fmat_residuals")
+    _lib.check(L.vgg_fmat_residuals(p1, p2, vm, Fb, B, N, res, _lib.stream_ptr()), "vgg_fmat_residuals")
     found = call[ar, best] >= 0
     mask = (res <= thr) & found[:, None]
     num = torch.where(found, call[ar, best], torch.zeros_like(top[:, 0]))

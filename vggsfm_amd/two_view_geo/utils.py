@@ -61,8 +61,7 @@ def sampson_epipolar_distance_batched(pts1, pts2, Fm, squared=True, eps=1e-8, de
     F = Fm.to(torch.float64).reshape(B * K, 9).contiguous()
     vm = torch.ones((B * K, N), dtype=torch.uint8, device=pts1.device)
     res = torch.empty((B * K, N), dtype=torch.float64, device=pts1.device)
-    _lib.check(_lib.lib().vgg_fmat_residuals(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(vm), _lib.ptr(F), B * K, N, _lib.ptr(res),
-                                             _lib.stream_ptr()), "vgg_fmat_residuals")
+    _lib.check(_lib.lib().vgg_fmat_residuals(p1, p2, vm, F, B * K, N, res, _lib.stream_ptr()), "vgg_fmat_residuals")
     res = res.reshape(B, K, N)
     return res if squared else (res + eps).sqrt()
 

@@ -26,14 +26,13 @@ def _launch_chunk(ext, tn_chunk, ivc_chunk, pairs, lo_num, max_angular_error, mi
     pts = torch.empty((n, 3), dtype=torch.float64, device=dev)
     num = torch.empty(n, dtype=torch.int64, device=dev)
     mask = torch.empty((n, S), dtype=torch.uint8, device=dev)
-    ws = torch.zeros(int(L.vgg_triangulate_workspace_bytes(S, n, H, lo_num)), dtype=torch.uint8, device=dev)
+    ws = torch.zeros(L.vgg_triangulate_workspace_bytes(S, n, H, lo_num), dtype=torch.uint8, device=dev)
     thr = ctypes.c_double(2.0 * math.pi + 1e-6)
     for _ in range(2):
         used = thr.value
-        _lib.check(L.vgg_triangulate_tracks(_lib.ptr(ext), _lib.ptr(tn_t), _lib.ptr(ivc_t), _lib.ptr(pairs_d), S, n, H,
-                                            lo_num, ctypes.c_double(max_angular_error), ctypes.c_double(min_tri_angle),
-                                            _lib.ptr(pts), _lib.ptr(num), _lib.ptr(mask), ctypes.byref(thr), _lib.ptr(ws),
-                                            _lib.stream_ptr()), "vgg_triangulate_tracks")
+        _lib.check(L.vgg_triangulate_tracks(ext, tn_t, ivc_t, pairs_d, S, n, H, lo_num, max_angular_error, min_tri_angle,
+                                            pts, num, mask, ctypes.byref(thr), ws, _lib.stream_ptr()),
+                   "vgg_triangulate_tracks")
         if thr.value == used:
             break
     return pts, num, mask.bool()
@@ -171,9 +170,8 @@ def triangulate_tracks(extrinsics, tracks_normalized, max_ransac_iters=256, lo_n
         ta, tb = min(n_loc, g0 * chunk_size), min(n_loc, g1 * chunk_size)
         if tb > ta:
             _lib.check(L.vgg_triangulate_tracks_chunks_enqueue(
-                _lib.ptr(ext), _lib.ptr(tn_t[ta:tb]), _lib.ptr(ivc_t[ta:tb]), _lib.ptr(pairs_dev[g0:g1]), S, tb - ta, H, g1 - g0,
-                chunk_size, lo, ctypes.c_double(max_angular_error), ctypes.c_double(min_tri_angle), _lib.ptr(pts[ta:tb]),
-                _lib.ptr(num[ta:tb]), _lib.ptr(mask[ta:tb]), _lib.ptr(thr_dev[g0:g1]), _lib.ptr(gmax_dev[g0:g1]), _lib.ptr(centers),
+                ext, tn_t[ta:tb], ivc_t[ta:tb], pairs_dev[g0:g1], S, tb - ta, H, g1 - g0, chunk_size, lo, max_angular_error,
+                min_tri_angle, pts[ta:tb], num[ta:tb], mask[ta:tb], thr_dev[g0:g1], gmax_dev[g0:g1], centers,
                 _lib.stream_ptr()), "vgg_triangulate_tracks_chunks_enqueue")
         pending, g_first = [], c + 1
     def raise_if_nonfinite(flag):
@@ -197,15 +195,13 @@ def triangulate_tracks(extrinsics, tracks_normalized, max_ransac_iters=256, lo_n
     if not (measured == first_thr).all():
         # (pathological: every hypothesis of a chunk has an inlier -- the threshold the launch assumed was not the chunk's
         #  maximum; run again with the measured ones, synchronously, as rounds 1-3 did)
-        ws = torch.zeros(int(L.vgg_triangulate_chunks_workspace_bytes(S, nc)), dtype=torch.uint8, device=dev)
+        ws = torch.zeros(L.vgg_triangulate_chunks_workspace_bytes(S, nc), dtype=torch.uint8, device=dev)
         thr = (ctypes.c_double * nc)(*[float(x) for x in measured])
         for _ in range(2):
             used = list(thr)
-            _lib.check(L.vgg_triangulate_tracks_chunks(_lib.ptr(ext), _lib.ptr(tn_t), _lib.ptr(ivc_t), _lib.ptr(pairs_dev), S, n_loc, H,
-                                                       nc, chunk_size, lo, ctypes.c_double(max_angular_error),
-                                                       ctypes.c_double(min_tri_angle), _lib.ptr(pts), _lib.ptr(num),
-                                                       _lib.ptr(mask), thr, _lib.ptr(ws), _lib.stream_ptr()),
-                       "vgg_triangulate_tracks_chunks")
+            _lib.check(L.vgg_triangulate_tracks_chunks(ext, tn_t, ivc_t, pairs_dev, S, n_loc, H, nc, chunk_size, lo,
+                                                       max_angular_error, min_tri_angle, pts, num, mask, thr, ws,
+                                                       _lib.stream_ptr()), "vgg_triangulate_tracks_chunks")
             if list(thr) == used:
                 break
     return pts, num, mask.bool()
@@ -235,8 +231,7 @@ def triangulate_by_pair(extrinsics, tracks_normalized, eps=1e-12):
     _lib.require_gpu(ext, tn)
     ext, tn = ext.contiguous(), tn.contiguous()
     pts = torch.empty((S - 1, N, 3), dtype=torch.float64, device=dev)
-    _lib.check(_lib.lib().vgg_triangulate_by_pair(_lib.ptr(ext), _lib.ptr(tn), S, N, _lib.ptr(pts), _lib.stream_ptr()),
-               "vgg_triangulate_by_pair")
+    _lib.check(_lib.lib().vgg_triangulate_by_pair(ext, tn, S, N, pts, _lib.stream_ptr()), "vgg_triangulate_by_pair")
     R, t = ext[:, :, :3], ext[:, :, 3]
     centers = -torch.einsum("sji,sj->si", R, t)
     z0 = torch.einsum("j,snj->sn", R[0, 2], pts) + t[0, 2]

@@ -51,14 +51,13 @@ def project_3D_points(points3D, extrinsics, intrinsics=None, extra_params=None, 
     want_cam = return_points_cam or only_points_cam
     out_cam = torch.empty((S, 3, P), dtype=torch.float64, device=dev) if want_cam else None
     if only_points_cam:
-        _lib.check(L.vgg_project_points(_lib.ptr(pts), P, _lib.ptr(ext), None, None, 0, S, None, _lib.ptr(out_cam),
-                                        _lib.stream_ptr()), "vgg_project_points")
+        _lib.check(L.vgg_project_points(pts, P, ext, None, None, 0, S, None, out_cam, _lib.stream_ptr()),
+                   "vgg_project_points")
         return out_cam
     K = _f64c(intrinsics)
     ep, k = _extra(extra_params)
     out_uv = torch.empty((S, P, 2), dtype=torch.float64, device=dev)
-    _lib.check(L.vgg_project_points(_lib.ptr(pts), P, _lib.ptr(ext), _lib.ptr(K), _lib.ptr(ep), k, S,
-                                    _lib.ptr(out_uv), _lib.ptr(out_cam), _lib.stream_ptr()), "vgg_project_points")
+    _lib.check(L.vgg_project_points(pts, P, ext, K, ep, k, S, out_uv, out_cam, _lib.stream_ptr()), "vgg_project_points")
     if return_points_cam:
         return out_uv, out_cam
     return out_uv
@@ -79,12 +78,9 @@ def filter_all_points3D(points3D, points2D, extrinsics, intrinsics, extra_params
     dev = pts.device
     mask = torch.empty(P, dtype=torch.uint8, device=dev)
     detail = torch.empty((S, P), dtype=torch.uint8, device=dev) if return_detail else None
-    ws = torch.empty(max(int(L.vgg_filter_points_workspace_bytes(S)), 8), dtype=torch.uint8, device=dev)
-    _lib.check(L.vgg_filter_points(_lib.ptr(pts), P, _lib.ptr(tr), is64, _lib.ptr(ext), _lib.ptr(K), _lib.ptr(ep), k, S,
-                                   ctypes.c_double(max_reproj_error), ctypes.c_double(min_tri_angle),
-                                   int(bool(check_triangle)), ctypes.c_double(hard_max), ctypes.c_double(behind_value),
-                                   _lib.ptr(mask), _lib.ptr(detail), _lib.ptr(ws), _lib.stream_ptr()),
-               "vgg_filter_points")
+    ws = torch.empty(max(L.vgg_filter_points_workspace_bytes(S), 8), dtype=torch.uint8, device=dev)
+    _lib.check(L.vgg_filter_points(pts, P, tr, is64, ext, K, ep, k, S, max_reproj_error, min_tri_angle, bool(check_triangle),
+                                   hard_max, behind_value, mask, detail, ws, _lib.stream_ptr()), "vgg_filter_points")
     return mask.bool(), (detail.bool() if return_detail else None)
 
 
@@ -101,11 +97,9 @@ def cam_from_img(pred_tracks, intrinsics, extra_params=None):
     max_it = 100
     ws = None
     if k:
-        ws = torch.empty(int(L.vgg_cam_from_img_workspace_bytes(S, P, max_it)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(L.vgg_cam_from_img_workspace_bytes(S, P, max_it), dtype=torch.uint8, device=dev)
     iters = ctypes.c_int(0)
-    _lib.check(L.vgg_cam_from_img(_lib.ptr(tr), is64, _lib.ptr(K), _lib.ptr(ep), k, S, P, _lib.ptr(out), max_it,
-                                  ctypes.c_double(1e-10), ctypes.c_double(1e-6),
-                                  ctypes.c_double(float(torch.finfo(torch.float64).eps)), _lib.ptr(ws),
+    _lib.check(L.vgg_cam_from_img(tr, is64, K, ep, k, S, P, out, max_it, 1e-10, 1e-6, torch.finfo(torch.float64).eps, ws,
                                   ctypes.byref(iters), _lib.stream_ptr()), "vgg_cam_from_img")
     return out
 

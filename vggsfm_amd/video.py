@@ -468,8 +468,6 @@ def point_colors(table, images, reverse=False, frame_chunk=None):
     frames at a time (default 16 for host frames, all at once on the device).  The sum runs in table order (ascending
     frame), so the result does not depend on the chunking or on where the frames live.
     Returns (rgb (P,3) float32, has_color (P,) bool) on the table's device: rgb = 0 where has_color is False."""
-    import ctypes
-
     if images.dim() == 5:
         if images.shape[0] != 1:
             raise ValueError(f"images: one video (1,T,3,H,W), got {tuple(images.shape)}")
@@ -513,14 +511,11 @@ def point_colors(table, images, reverse=False, frame_chunk=None):
                     staging = torch.empty((chunk, 3, H, W), dtype=torch.float32, device=dev)
                 frames = staging[:f1 - f0]
                 frames.copy_(images[f0:f1], non_blocking=images.is_pinned())
-            _lib.check(L.vgg_color_gather(_lib.ptr(frames), ctypes.c_int(f0), ctypes.c_int(f1), ctypes.c_int(H),
-                                          ctypes.c_int(W), ctypes.c_int(1 if reverse else 0), _lib.ptr(order),
-                                          ctypes.c_long(row_ptr[f0]), ctypes.c_long(row_ptr[f1]), _lib.ptr(table.obs_frame),
-                                          _lib.ptr(table.obs_uv), ctypes.c_long(O), _lib.ptr(gathered), _lib.ptr(bad),
-                                          stream), "vgg_color_gather")
+            _lib.check(L.vgg_color_gather(frames, f0, f1, H, W, bool(reverse), order, row_ptr[f0], row_ptr[f1],
+                                          table.obs_frame, table.obs_uv, O, gathered, bad, stream), "vgg_color_gather")
     point_ptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
-    _lib.check(L.vgg_color_reduce(_lib.ptr(table.obs_point), ctypes.c_long(O), ctypes.c_long(P), _lib.ptr(gathered),
-                                  _lib.ptr(point_ptr), _lib.ptr(rgb), _lib.ptr(has), _lib.stream_ptr()), "vgg_color_reduce")
+    _lib.check(L.vgg_color_reduce(table.obs_point, O, P, gathered, point_ptr, rgb, has, _lib.stream_ptr()),
+               "vgg_color_reduce")
     b = int(bad.item()) if O else 2 ** 31 - 1
     if b != 2 ** 31 - 1:
         p, f = int(table.obs_point[b]), int(table.obs_frame[b])
