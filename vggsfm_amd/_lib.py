@@ -6,7 +6,9 @@ a product function that needs it raises.  torch is imported first so that the li
 
 The C type of every argument of every entry is declared once, in ``SIGNATURES`` below, and applied when the library is
 loaded: callers pass tensors, ``None``, ints and floats as they are.  A new C-ABI entry needs one prototype in the
-header and one row in that table (tests/test_host_logic.py compares the two, type by type).
+header and one row in that table (tests/test_host_logic.py compares the two, type by type).  include/vggsfm_amd.h and
+``SIGNATURES`` are a closed set; the multi-view entries (include/vggsfm_amd_multiview.h, prefix ``vggx_``) have the table
+``SIGNATURES_MULTIVIEW``, applied next to the first.
 """
 import ctypes
 import operator
@@ -149,6 +151,20 @@ SIGNATURES = {
 }
 EXPORTED = list(SIGNATURES)
 
+# The second table: the vggx_* entries of include/vggsfm_amd_multiview.h (csrc/multiview.hip, same library), in that header's
+# order.  tests/test_multiview_host.py compares it with that header as tests/test_host_logic.py compares the first.
+SIGNATURES_MULTIVIEW = {
+    "vggx_multiview_workspace_bytes": (_SIZE, [_L, _I]),
+    "vggx_view_centers": (_INT, [_P, _L, _P, _P]),
+    "vggx_multiview_triangulate": (_INT, [_P, _L, _I, _P, _I, _L, _L, _P, _I, _L, _L, _P, _L, _I, _I, _I, _D, _P, _P, _P, _P,
+                                          _P, _P]),
+    "vggx_max_tri_angle": (_INT, [_P, _L, _I, _P, _L, _I, _I, _D, _P, _P, _P, _P]),
+    "vggx_tri_angle_table": (_INT, [_P, _L, _P, _L, _I, _D, _P, _P, _P]),
+    "vggx_tri_angle_pairs": (_INT, [_P, _P, _L, _P, _L, _D, _P, _P]),
+    "vggx_angular_error": (_INT, [_P, _P, _P, _L, _L, _L, _I, _P, _P, _P]),
+}
+EXPORTED_MULTIVIEW = list(SIGNATURES_MULTIVIEW)
+
 _lib = None
 
 
@@ -176,9 +192,10 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in (SIGNATURES, SIGNATURES_MULTIVIEW):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

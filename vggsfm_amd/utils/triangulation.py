@@ -11,6 +11,7 @@ import math
 import torch
 
 from .. import _lib
+from . import triangulation_helpers as _H
 from .triangulation_helpers import generate_combinations
 
 
@@ -248,6 +249,67 @@ def triangulate_by_pair(extrinsics, tracks_normalized, eps=1e-12):
     ang = torch.abs(torch.acos(torch.clamp(nom / den, -1.0, 1.0)))
     ang = torch.min(ang, torch.pi - ang) * (180.0 / torch.pi)
     return pts, cheirality, ang
+
+
+def triangulate_tracks_masked(extrinsics, tracks_normalized, view_weight=None, min_tri_angle=None):
+    """Masked multi-view DLT of every track over a GIVEN set of views (no RANSAC): the lean form the namesakes
+    `triangulate_multi_view_point_batched`, `triangulate_multi_view_point_from_tracks` and `local_refinement_tri` share
+    their kernels with (csrc/multiview.hip).  extrinsics (S,3,4), tracks_normalized (S,N,2) float32 or float64 in the
+    package's own layout, view_weight (S,N) bool or float (None: every view) ->
+    (points (N,3) f64, valid_cheirality (N) bool, max_tri_angle (N) f64 degrees [, max_tri_angle >= min_tri_angle (N) bool]).
+    The weight multiplies the view's 3x4 DLT term, so a float weight enters squared; the point is the eigenvector of the
+    smallest eigenvalue of the 4x4 normal matrix over its last component; cheirality fails when z <= 0 in ANY of the S views,
+    weighted or not; the angle is the largest over all S x S camera pairs, as in the reference's table.  One camera set
+    serves all points: neither per-point cameras nor the S*S table exist.  A track with fewer than two views of non-zero
+    weight has no defined answer: NaN point, valid_cheirality False, angle 0 (flag False)."""
+    S, N = tracks_normalized.shape[0], tracks_normalized.shape[1]
+    assert tuple(extrinsics.shape) == (S, 3, 4) and tuple(tracks_normalized.shape) == (S, N, 2)
+    assert view_weight is None or tuple(view_weight.shape) == (S, N)
+    _lib.require_gpu(extrinsics, tracks_normalized, view_weight)
+    ext = extrinsics.to(torch.float64).contiguous()
+    tr, is64 = _H._tracks_arg(tracks_normalized)
+    w, kind = _H._mv_weights(view_weight)
+    pts, inv, ang, flag = _H._mv_solve(ext, 1, 1, tr, is64, (2, 2 * N), w, kind, (1, N), None, N, S, angle_mode=1,
+                                       min_tri_angle=min_tri_angle)
+    out = (pts, ~inv.bool(), ang)
+    return out if min_tri_angle is None else out + (flag.bool(),)
+
+
+def max_triangulation_angle(extrinsics, points3D, min_tri_angle=None):
+    """The reduced angle pass on its own: extrinsics (S,3,4), points3D (N,3) -> largest triangulation angle in degrees over
+    all camera pairs (N) f64 [, >= min_tri_angle (N) bool].  A non-finite point gives 0 (False)."""
+    S, N = extrinsics.shape[0], points3D.shape[0]
+    assert tuple(extrinsics.shape) == (S, 3, 4) and tuple(points3D.shape) == (N, 3)
+    _lib.require_gpu(extrinsics, points3D)
+    L = _lib.lib()
+    dev = points3D.device
+    ang = torch.empty(N, dtype=torch.float64, device=dev)
+    flag = torch.empty(N, dtype=torch.uint8, device=dev) if min_tri_angle is not None else None
+    ws = torch.empty(max(L.vggx_multiview_workspace_bytes(1, S), 8), dtype=torch.uint8, device=dev)
+    _lib.check(L.vggx_max_tri_angle(extrinsics.to(torch.float64).contiguous(), 1, 1, points3D.to(torch.float64).contiguous(),
+                                    N, S, 1, 0.0 if min_tri_angle is None else min_tri_angle, ang, flag, ws,
+                                    _lib.stream_ptr()), "vggx_max_tri_angle")
+    return ang if min_tri_angle is None else (ang, flag.bool())
+
+
+def triangulate_multi_view_point_from_tracks(cams_from_world, tracks, mask=None):
+    """Reference: triangulation.py:650-674.  cams_from_world (B,S,3,4), tracks (B,S,N,2), mask (B,S,N) ->
+    (points3d (B,N,3) f64, cheirality_mask (B,N) bool).  One launch per batch element on its shared cameras; the reference
+    expands them to (B*N,S,3,4)."""
+    B, S, _, _ = cams_from_world.shape
+    _, _, N, _ = tracks.shape
+    assert tuple(cams_from_world.shape) == (B, S, 3, 4) and tuple(tracks.shape) == (B, S, N, 2)
+    assert mask is None or tuple(mask.shape) == (B, S, N)
+    _lib.require_gpu(cams_from_world, tracks, mask)
+    points3d = torch.empty((B, N, 3), dtype=torch.float64, device=tracks.device)
+    cheirality = torch.empty((B, N), dtype=torch.bool, device=tracks.device)
+    for b in range(B):
+        tr, is64 = _H._tracks_arg(tracks[b])
+        w, kind = _H._mv_weights(None if mask is None else mask[b])
+        pts, inv, _, _ = _H._mv_solve(cams_from_world[b].to(torch.float64).contiguous(), 1, 1, tr, is64, (2, 2 * N), w, kind,
+                                      (1, N), None, N, S)
+        points3d[b], cheirality[b] = pts, ~inv.bool()
+    return points3d, cheirality
 
 
 # ==========================================================================================

@@ -134,3 +134,166 @@ def generate_combinations(N):
     order from `np.triu_indices`."""
     i, j = np.triu_indices(N, 1)
     return np.stack([i, j], 1).astype(np.int64).reshape(-1, 2)
+
+
+# ==========================================================================================
+# Masked multi-view triangulation and the angle helpers (csrc/multiview.hip, include/vggsfm_amd_multiview.h).
+# float64 throughout, whatever the input precision (INTEGRATION.md section 6).
+# ==========================================================================================
+MAX_ANGLE_TABLE_BYTES = 2 ** 31        # size guard of the namesakes that return a (B, S*S) / (S*S, P) angle table
+_LEAN = "vggsfm_amd.utils.triangulation.triangulate_tracks_masked"
+
+
+def _guard_table(rows, cols, what):
+    nbytes = 8 * int(rows) * int(cols)
+    if nbytes > MAX_ANGLE_TABLE_BYTES:
+        raise ValueError(f"{what}: the ({rows}, {cols}) float64 angle table would take {nbytes} bytes, more than "
+                         f"MAX_ANGLE_TABLE_BYTES = {MAX_ANGLE_TABLE_BYTES}; {_LEAN} returns the largest angle per point "
+                         "(and the >= min_tri_angle flag) without the table")
+
+
+def _mv_weights(w):
+    """mask / weights -> (tensor or None, weight_kind of vggx_multiview_triangulate): bool as bytes, anything else float64."""
+    if w is None:
+        return None, 0
+    if w.dtype == torch.bool:
+        return w.contiguous().view(torch.uint8), 1
+    return _f64c(w), 2
+
+
+def _mv_solve(cams, cam_groups, group_div, tracks, is64, track_strides, weights, weight_kind, weight_strides, weight_rows,
+              n, S, zero_masked=False, angle_mode=0, min_tri_angle=None):
+    """One vggx_multiview_triangulate call -> (points (n,3) f64, invalid cheirality (n) u8, max angle (n) | None,
+    angle flag (n) u8 | None).  The tensors are contiguous and on the device already."""
+    L = _lib.lib()
+    dev = tracks.device
+    pts = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    inv = torch.empty(n, dtype=torch.uint8, device=dev)
+    ang = torch.empty(n, dtype=torch.float64, device=dev) if angle_mode == 1 else None
+    flag = torch.empty(n, dtype=torch.uint8, device=dev) if angle_mode == 2 or (angle_mode == 1 and min_tri_angle is not None) \
+        else None
+    ws = torch.empty(max(L.vggx_multiview_workspace_bytes(cam_groups, S), 8), dtype=torch.uint8, device=dev) if angle_mode \
+        else None
+    _lib.check(L.vggx_multiview_triangulate(cams, cam_groups, group_div, tracks, is64, track_strides[0], track_strides[1],
+                                            weights, weight_kind, weight_strides[0], weight_strides[1], weight_rows, n, S,
+                                            bool(zero_masked), angle_mode, 0.0 if min_tri_angle is None else min_tri_angle,
+                                            pts, inv, ang, flag, ws, _lib.stream_ptr()), "vggx_multiview_triangulate")
+    return pts, inv, ang, flag
+
+
+def _cams_arg(cams):
+    """(B,S,3,4) cameras -> (contiguous f64 tensor, cam_groups): ONE set when the batch axis is an expanded view."""
+    if cams.shape[0] > 1 and cams.stride(0) == 0:
+        return _f64c(cams[0]), 1
+    return _f64c(cams), cams.shape[0]
+
+
+def _angle_table(cams, cam_groups, points3D, B, S, eps):
+    L = _lib.lib()
+    out = torch.empty((B, S * S), dtype=torch.float64, device=points3D.device)
+    ws = torch.empty(max(L.vggx_multiview_workspace_bytes(cam_groups, S), 8), dtype=torch.uint8, device=points3D.device)
+    _lib.check(L.vggx_tri_angle_table(cams, cam_groups, points3D, B, S, eps, out, ws, _lib.stream_ptr()),
+               "vggx_tri_angle_table")
+    return out
+
+
+def triangulate_multi_view_point_batched(cams_from_world, points, mask=None, compute_tri_angle=False,
+                                         check_cheirality=False):
+    """Reference: triangulation_helpers.py:27-131.  cams_from_world (B,N,3,4), points (B,N,2), mask (B,N) bool or weights
+    -> points (B,3) f64 [, angles (B,N*N) degrees] [, invalid cheirality (B) bool].  The mask multiplies the per-view
+    DLT term (float weights enter squared); cheirality looks at ALL N views; the angle table covers all N x N ordered
+    pairs.  A batch axis that is an expanded view (stride 0) is read as one shared camera set.  A point with fewer than
+    two views of non-zero weight comes back NaN with invalid cheirality (the reference: an arbitrary null vector)."""
+    B, N, _ = points.shape
+    assert cams_from_world.shape[0] == B and cams_from_world.shape[1] == N, \
+        "The number of cameras and points must be equal for each batch."
+    assert mask is None or tuple(mask.shape) == (B, N), "mask must be BxN"
+    if compute_tri_angle:
+        _guard_table(B, N * N, "triangulate_multi_view_point_batched(compute_tri_angle=True)")
+    _lib.require_gpu(cams_from_world, points, mask)
+    cams, groups = _cams_arg(cams_from_world)
+    tr, is64 = _tracks_arg(points)
+    w, kind = _mv_weights(mask)
+    pts, inv, _, _ = _mv_solve(cams, groups, 1, tr, is64, (2 * N, 2), w, kind, (N, 1), None, B, N)
+    out = (pts,)
+    if compute_tri_angle:
+        out += (_angle_table(cams, groups, pts, B, N, 1e-12),)
+    if check_cheirality:
+        out += (inv.bool(),)
+    return out if len(out) > 1 else pts
+
+
+def calculate_triangulation_angle_batched(extrinsics, points3D, eps=1e-12):
+    """Reference: triangulation_helpers.py:475-521.  extrinsics (B,S,3,4), points3D (B,3) -> (B,S*S) degrees, all ordered
+    pairs in row-major order (the diagonal is 0)."""
+    B, S, _, _ = extrinsics.shape
+    assert len(points3D) == B
+    _guard_table(B, S * S, "calculate_triangulation_angle_batched")
+    _lib.require_gpu(extrinsics, points3D)
+    cams, groups = _cams_arg(extrinsics)
+    return _angle_table(cams, groups, _f64c(points3D), B, S, eps)
+
+
+def calculate_triangulation_angle(proj_center1, proj_center2, point3D, eps=1e-12):
+    """Reference: triangulation_helpers.py:547-587.  proj_center1/2 (K,3), point3D (P,3) -> (K,P) degrees."""
+    K, P = proj_center1.shape[0], point3D.shape[0]
+    assert tuple(proj_center1.shape) == (K, 3) and tuple(proj_center2.shape) == (K, 3) and tuple(point3D.shape) == (P, 3)
+    _guard_table(K, P, "calculate_triangulation_angle")
+    _lib.require_gpu(proj_center1, proj_center2, point3D)
+    out = torch.empty((K, P), dtype=torch.float64, device=point3D.device)
+    _lib.check(_lib.lib().vggx_tri_angle_pairs(_f64c(proj_center1), _f64c(proj_center2), K, _f64c(point3D), P, eps, out,
+                                               _lib.stream_ptr()), "vggx_tri_angle_pairs")
+    return out
+
+
+def calculate_triangulation_angle_exhaustive(extrinsics, points3D):
+    """Reference: triangulation_helpers.py:524-544.  extrinsics (S,3,4), points3D (P,3) -> (S*S,P) degrees."""
+    S, P = extrinsics.shape[0], points3D.shape[0]
+    assert tuple(extrinsics.shape) == (S, 3, 4) and tuple(points3D.shape) == (P, 3)
+    _guard_table(S * S, P, "calculate_triangulation_angle_exhaustive")
+    _lib.require_gpu(extrinsics, points3D)
+    centers = torch.empty((S, 3), dtype=torch.float64, device=points3D.device)
+    _lib.check(_lib.lib().vggx_view_centers(_f64c(extrinsics), S, centers, _lib.stream_ptr()), "vggx_view_centers")
+    c1 = centers[:, None].expand(-1, S, -1).reshape(S * S, 3)
+    c2 = centers[None].expand(S, -1, -1).reshape(S * S, 3)
+    return calculate_triangulation_angle(c1, c2, points3D)
+
+
+def calculate_normalized_angular_error_batched(point2D, point3D, cam_from_world, to_degree=False):
+    """Reference: triangulation_helpers.py:431-472.  point2D (B,N,2), point3D (P,N,3), cam_from_world (B,3,4) ->
+    (angle (P,B,N) radians or degrees, cos_angle (P,B,N) clamped to [-1,1])."""
+    B, N, _ = point2D.shape
+    P, _, _ = point3D.shape
+    assert len(cam_from_world) == B
+    assert point3D.shape[1] == N and point3D.shape[2] == 3 and point2D.shape[2] == 2
+    _lib.require_gpu(point2D, point3D, cam_from_world)
+    dev = point2D.device
+    ang = torch.empty((P, B, N), dtype=torch.float64, device=dev)
+    cos = torch.empty((P, B, N), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().vggx_angular_error(_f64c(point2D), _f64c(point3D), _f64c(cam_from_world), B, N, P, bool(to_degree),
+                                             ang, cos, _lib.stream_ptr()), "vggx_angular_error")
+    return ang, cos
+
+
+def local_refinement_tri(points1, extrinsics, min_tri_angle, inlier_mask, sorted_indices, lo_num=50, low_mem=True):
+    """Reference: triangulation_helpers.py:648-725.  points1 (B,N,2), extrinsics (B,N,3,4), inlier_mask (B,H,N) bool,
+    sorted_indices (B,H) -> (points (B,lo_num,3) f64, tri_angle_masks (B,lo_num) bool, invalid_che_mask (B,lo_num) bool).
+    Candidate l of track b is the DLT over the views inlier_mask[b, sorted_indices[b, l]] selects (the other observations
+    are read as zero and carry no weight); all B x lo_num solves are one launch, each track's cameras read by its
+    candidates, and the "some pair of the N cameras subtends >= min_tri_angle" test stops at the first such pair.
+    `low_mem` is accepted and changes nothing: neither form of the reference's loop exists here."""
+    B, N, _ = points1.shape
+    assert extrinsics.shape[0] == B and extrinsics.shape[1] == N
+    H = inlier_mask.shape[1]
+    assert tuple(inlier_mask.shape) == (B, H, N) and sorted_indices.shape[0] == B and sorted_indices.shape[1] >= lo_num >= 1
+    _lib.require_gpu(points1, extrinsics, inlier_mask, sorted_indices)
+    lo_indices = sorted_indices[:, :lo_num].to(torch.int64)
+    if B > 0 and not bool(((lo_indices >= -H) & (lo_indices < H)).all()):
+        raise IndexError(f"local_refinement_tri: sorted_indices outside the {H} hypotheses of inlier_mask")
+    rows = (torch.arange(B, device=points1.device)[:, None] * H + lo_indices % H).reshape(-1).contiguous()
+    cams, groups = _cams_arg(extrinsics)
+    tr, is64 = _tracks_arg(points1)
+    w, kind = _mv_weights(inlier_mask.bool())
+    pts, inv, _, flag = _mv_solve(cams, groups, lo_num, tr, is64, (2 * N, 2), w, kind, (N, 1), rows, B * lo_num, N,
+                                  zero_masked=True, angle_mode=2, min_tri_angle=min_tri_angle)
+    return pts.view(B, lo_num, 3), flag.view(B, lo_num).bool(), inv.view(B, lo_num).bool()
