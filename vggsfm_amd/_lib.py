@@ -8,7 +8,8 @@ The C type of every argument of every entry is declared once, in ``SIGNATURES`` 
 loaded: callers pass tensors, ``None``, ints and floats as they are.  A new C-ABI entry needs one prototype in the
 header and one row in that table (tests/test_host_logic.py compares the two, type by type).  include/vggsfm_amd.h and
 ``SIGNATURES`` are a closed set; the multi-view entries (include/vggsfm_amd_multiview.h, prefix ``vggx_``) have the table
-``SIGNATURES_MULTIVIEW``, applied next to the first.
+``SIGNATURES_MULTIVIEW``, applied next to the first, and the essential-matrix entries (include/vggsfm_amd_essential.h, prefix
+``vgge_emat_``) the table ``SIGNATURES_ESSENTIAL``.
 """
 import ctypes
 import operator
@@ -165,6 +166,16 @@ SIGNATURES_MULTIVIEW = {
 }
 EXPORTED_MULTIVIEW = list(SIGNATURES_MULTIVIEW)
 
+# The third table: the vgge_emat_* entries of include/vggsfm_amd_essential.h (csrc/essential.hip, same library), in that
+# header's order.  tests/test_essential_host.py compares the two.
+SIGNATURES_ESSENTIAL = {
+    "vgge_emat_five_point": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "vgge_emat_solve": (_INT, [_P, _P, _P, _L, _I, _P, _P, _P]),
+    "vgge_emat_score": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "vgge_emat_refine": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+}
+EXPORTED_ESSENTIAL = list(SIGNATURES_ESSENTIAL)
+
 _lib = None
 
 
@@ -192,7 +203,7 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for table in (SIGNATURES, SIGNATURES_MULTIVIEW):
+    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -17,13 +17,13 @@
 //   fmat_residuals_kernel  residuals of the winner (B x N)
 // Selection of the lo_num best hypotheses (a stable sort of K integers per pair) is left to the caller.
 #include "common.hpp"
+#include "two_view.hpp"
 #include "../../include/vggsfm_amd.h"
 
 namespace vgg {
 
 constexpr int kBisections = 110;     // BISECTIONS in oracle/fundamental.py
 constexpr int kSweeps9 = 10, kSweeps3 = 8;
-constexpr double kBig = 1e6;         // residual of an invalid match
 
 // ------------------------------------------------------------------------------------------------ small solvers
 // real roots of c3 x^3 + c2 x^2 + c1 x + c0 (oracle: cubic_real_roots)
@@ -99,15 +99,6 @@ __device__ inline double denormalize_unit(const double* Fh, const double* T1, co
 #pragma unroll
   for (int i = 0; i < 9; ++i) F[i] = F[i] / n;
   return n;
-}
-
-__device__ inline void jacobi_cs(double app, double aqq, double apq, double& c, double& s) {
-  const bool rot = apq != 0.0;
-  const double tau = (aqq - app) / (2.0 * (rot ? apq : 1.0));
-  const double t = ((tau >= 0.0) ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-  const double cc = 1.0 / sqrt(1.0 + t * t);
-  c = rot ? cc : 1.0;
-  s = rot ? t * cc : 0.0;
 }
 
 // cyclic Jacobi of a symmetric 3x3 (scalar): eigenvector of the smallest eigenvalue (first minimum)
@@ -246,18 +237,6 @@ __global__ __launch_bounds__(64) void fmat7_kernel(const double* __restrict__ pt
 }
 
 // ------------------------------------------------------------------------------------------------ residuals
-__device__ inline double sampson_sq(const double* __restrict__ F, double u1, double v1, double u2, double v2) {
-  const double l0 = (F[0] * u1 + F[1] * v1) + F[2];
-  const double l1 = (F[3] * u1 + F[4] * v1) + F[5];
-  const double l2 = (F[6] * u1 + F[7] * v1) + F[8];
-  const double m0 = (F[0] * u2 + F[3] * v2) + F[6];
-  const double m1 = (F[1] * u2 + F[4] * v2) + F[7];
-  const double num = (u2 * l0 + v2 * l1) + l2;
-  const double den = (l0 * l0 + l1 * l1) + (m0 * m0 + m1 * m1);
-  const double r = (num * num) / den;
-  return isfinite(r) ? r : kBig;
-}
-
 constexpr int kHypPerWave = 4;   // hypotheses scored per sweep of a wavefront: the points are read once for all of them
 
 __global__ __launch_bounds__(256) void fmat_score_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
@@ -323,25 +302,6 @@ __global__ __launch_bounds__(256) void fmat_residuals_kernel(const double* __res
 }
 
 // ------------------------------------------------------------------------------------------------ 8-point
-// fixed-order reduction of Q quantities over the 256 threads: halving tree (t, t + 128), (t, t + 64), ...
-template <int Q>
-__device__ inline void block_tree_sum(double (*red)[256], const double* val, double* out) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) red[q][tid] = val[q];
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) red[q][tid] = red[q][tid] + red[q][tid + st];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < Q; ++q) out[q] = red[q][0];
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(256) void fmat8_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
                                                    const uint8_t* __restrict__ vmask, const double* __restrict__ Fsrc,
                                                    const int32_t* __restrict__ src_counts, const int32_t* __restrict__ sel,

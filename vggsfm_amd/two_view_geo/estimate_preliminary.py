@@ -11,7 +11,8 @@ otherwise); ``preliminary_dict`` = fmat, fmat_inlier_mask, fmat_residuals, R_ope
 (+ fmat_inlier_num).  The runner keeps only the dict (vggsfm/runners/runner.py:478) and the Triangulator only reads
 ``fmat_inlier_mask``.  The reference's 5-point essential and 4-point homography RANSACs (essential.py, homography.py)
 are not called by this function there either (`predict_essential` / `predict_homo` are dead parameters: "TODO: also clean
-the code", :115) and are not provided."""
+the code", :115); the 5-point RANSAC is provided on its own as ``vggsfm_amd.two_view_geo.estimate_essential``, the
+homography RANSAC is not provided."""
 import types
 
 import torch
