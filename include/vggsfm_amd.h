@@ -354,7 +354,15 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
  * factors; round 6): every thread adds one tile row's products for two of a batch's entries -- no second camera-major evaluation
  * of the projections per iteration; 1 = the tile launch for 6 x 6 blocks only, the camera pass cam_pass<RHS> for the others (the
  * round-4/5 behaviour); 0 = the camera pass always.  All compute the same system up to the order of its sums.  Requires
- * entries[e][0] = the entry's point. */
+ * entries[e][0] = the entry's point.
+ * Bit 2 (value | 4; A/B measurements and tests): keep the glue of an LM iteration as separate launches -- tile sums, assembly,
+ * preparation, step sums -- instead of the merged ones; the same bits either way.
+ * Host-side state (the only one of this API): vgg_ba_begin notes, per WORKSPACE ADDRESS, that the preparation launch is still
+ * due in front of the first point pass, and whether every camera group has a diagonal tile -- for which it copies the tile
+ * table (16 bytes per tile) to the host and synchronises the stream ONCE per solve.  The table holds the 64 most recently begun
+ * workspaces (mutex-protected, oldest replaced first); an entry lives until vgg_ba_begin is called again on that address or 64
+ * other workspaces have begun.  A phase call on a workspace the table does not know takes the separate launches: same results,
+ * three launches more per iteration. */
 int vgg_ba_set_tile_rhs(int enable);
 int vgg_ba_profile(int enable, int max_launches_per_kernel);
 int vgg_ba_profile_read(int kernel_id, double* total_ms, int* launches, int reset);

@@ -176,7 +176,8 @@ class DeviceProblem:
 # Measurement hooks.  The product path reads NO environment variable unless VGGSFM_AMD_DEBUG_HOOKS=1 is set (the A/B harness
 # scripts/prof/ab_c3.py sets it): then VGGSFM_QUAD_SORT_WINDOW, VGGSFM_TILE_TOP_UP, VGGSFM_TILE_ORDER, VGGSFM_TILE_COST_MODE,
 # VGGSFM_TILE_FIXED_COST, VGGSFM_TILE_POS_WEIGHT, VGGSFM_SORT_POINTS, VGGSFM_TILE_WGS and VGGSFM_TILE_BACKFILL override the
-# constants below, all read per call (A/B runs switch them in-process).  Every one of them changes the SCHEDULE of the work,
+# constants below, and VGGSFM_LEGACY_GLUE=1 keeps the separate glue launches of an LM iteration (solve), all read per call
+# (A/B runs switch them in-process).  Every one of them changes the SCHEDULE of the work,
 # never a sum: results are bit-identical across their values (tests/test_gpu_ba.py).
 def _hook(name, default=None):
     if os.environ.get("VGGSFM_AMD_DEBUG_HOOKS") != "1":
@@ -901,8 +902,16 @@ def _summary_dict(summ, log, n):
 
 
 def solve(problem: DeviceProblem, options: Optional[BundleAdjustmentOptions] = None, workspace=None):
-    """Run the LM loop of `problem` in place on the current stream; one host sync at the end."""
+    """Run the LM loop of `problem` in place on the current stream.  Host syncs: one at the start (vgg_ba_begin reads the tile
+    table, a few KB, to see whether every camera group has a diagonal tile), the `done` poll every eighth iteration, and one
+    at the end."""
     L = _lib.lib()
+    # measurement hook: "1" = the separate glue launches, "0" = the merged ones.  Either value also sets the right-hand-side
+    # mode to 2 (the default): vgg_ba_set_tile_rhs takes both in one integer and has no getter, so a harness that chose mode
+    # 0 / 1 must not set this variable (scripts/prof/ab_c3.py does not)
+    glue = _hook("VGGSFM_LEGACY_GLUE")
+    if glue is not None:
+        L.vgg_ba_set_tile_rhs(2 | (4 if glue == "1" else 0))
     options = options or BundleAdjustmentOptions()
     problem.refine_focal = options.refine_focal_length
     problem.refine_extra = options.refine_extra_params

@@ -26,7 +26,9 @@
 //   cam_pass<CAND>  the same camera-major pass at the candidate: its cost decides the step, and on acceptance its U_c, g_c
 //                   are the next linearisation (no pass at the start of the next iteration)
 //   control         Ceres' accept / reject logic, one workgroup
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "camera_model.hpp"
 #include "../../include/vggsfm_amd.h"
@@ -86,7 +88,10 @@ constexpr int kPackPad = 1024;    // >= ranks of a sharded solve (padding of the
 struct Ctl {
   double radius, decrease_factor, x_cost, initial_cost, gmax_cams, gmax, cand_cost, mcc, step_norm, rel;
   int32_t iteration, done, termination, need_lin, scale_ready, invalid_streak, num_succ, num_unsucc;
-  int32_t linear_fail, accept, rank, world, grad_logged, pad0, pad1, pad2;
+  int32_t linear_fail, accept, rank, world, grad_logged;
+  int32_t step_arrivals;          // cam_reduce workgroups of the candidate's linearisation that have stored (the last one sums)
+  // how often this solve ran the merged glue: tile_assemble_kernel launches, step sums in cam_reduce_kernel (tests read them)
+  int32_t merged_glue_launches, merged_step_sums;
 };
 
 struct Dims {
@@ -166,8 +171,10 @@ static Dims make_dims(const vgg_ba_problem* pb) {
 }
 
 // overrides of the automatic launch choices (vgg_ba_tuning, vgg_ba_set_tile_rhs): 0 / -1 = automatic
-struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs; };
-static Tuning g_tuning = {0, -1, 0, 0, 2};
+// legacy_glue (vgg_ba_set_tile_rhs(| 4), A/B runs and tests): tile sums, assembly, preparation and the step sums as the separate
+// launches they were before they were merged (tile_assemble_kernel, cam_reduce_kernel's last arriver)
+struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs, legacy_glue; };
+static Tuning g_tuning = {0, -1, 0, 0, 2, 0};
 
 static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, void* base) {
   Ws w;
@@ -515,12 +522,40 @@ __global__ __launch_bounds__(256, (MODE == 1) ? VGG_CP_OCC_RHS : VGG_CP_OCC) voi
   if (threadIdx.x < NV) w.cam_split[((size_t)c * kCamSplitMax + blockIdx.y) * kCamNV + threadIdx.x] = tot[threadIdx.x];
 }
 
-// sums the `split` slices of a camera in order and stores U, g, cost (MODE 0) or T (MODE 1)
+// reduce buffer 3: [0] the candidate's cost (sum over the cameras of cam_pass<CAND>'s sums), [1..3] the point_step sums.
+// 256 threads; BYPASS: the partial sums were stored by other workgroups of the SAME launch (cam_reduce_kernel's last arriver)
+// and are loaded past this CU's L1.
+template <bool BYPASS>
+__device__ __forceinline__ void reduce_step_body(const Ws& w, int nparts, int C, double (*red)[256]) {
+  auto ld = [](const double* p) -> double {
+    return BYPASS ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+  };
+  double s[4] = {0, 0, 0, 0};
+  for (int i = threadIdx.x; i < C; i += 256) s[0] += ld(w.cost_cand + i);
+  for (int i = threadIdx.x; i < nparts; i += 256)
+    for (int k = 1; k < 4; ++k) s[k] += ld(w.part_F + 4 * i + k);
+  for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) w.stepsum[threadIdx.x] = red[threadIdx.x][0];
+}
+
+// sums the `split` slices of a camera in order and stores U, g, cost (MODE 0) or T (MODE 1).
+// MODE 0 runs with 256 threads (reduce_step_body's tree); step_parts > 0 (the candidate's linearisation, phase 2): the workgroup
+// that arrives LAST at ctl->step_arrivals also sums reduce buffer 3 from the cameras' costs and point_step's `step_parts`
+// partial sums -- it needs nothing but "every camera's cost is stored", so no launch of its own.  Nobody waits: each workgroup
+// drains its stores, releases them at agent scope and takes a ticket; the one that draws C - 1 acquires and reads past its L1.
+// The last arriver puts the counter back to 0 (init_kernel clears it once per solve), so an iteration that was cut short --
+// ctl->done: no workgroup takes a ticket -- leaves it at 0 as well.
 template <int KD, int MODE>
-__global__ __launch_bounds__(64) void cam_reduce_kernel(DevProblem pb, Ws w, int split, int point_parts) {
+__global__ __launch_bounds__(MODE == 0 ? 256 : 64) void cam_reduce_kernel(DevProblem pb, Ws w, int split, int point_parts, int step_parts) {
   constexpr int BD = 6 + KD;
   constexpr int NU = BD * (BD + 1) / 2;
   constexpr int NV = (MODE == 0) ? (NU + BD + 1) : (BD * (1 + KD));
+  __shared__ double red[MODE == 0 ? 4 : 1][MODE == 0 ? 256 : 1];
   if (w.ctl->done) return;
   if (MODE == 1 && blockIdx.x == 0) {            // (rides along: max of the point passes' per-workgroup gradient norms)
     double m = 0;
@@ -530,27 +565,53 @@ __global__ __launch_bounds__(64) void cam_reduce_kernel(DevProblem pb, Ws w, int
   }
   const Dims& d = pb.d;
   const int c = blockIdx.x, kdsh = d.kdsh;
-  if (threadIdx.x >= NV) return;
-  double tot = 0.0;
+  if (threadIdx.x < NV) {
+    double tot = 0.0;
 #pragma unroll 8
-  for (int sp = 0; sp < split; ++sp) tot += w.cam_split[((size_t)c * kCamSplitMax + sp) * kCamNV + threadIdx.x];
-  if (MODE == 0) {
-    double* U = w.U + (size_t)c * BD * BD;
-    if (threadIdx.x < NU) {
-      int i = 0, rem = threadIdx.x;
-      while (rem >= BD - i) { rem -= BD - i; ++i; }
-      const int k = i + rem;
-      U[i * BD + k] = tot;
-      U[k * BD + i] = tot;
-    } else if (threadIdx.x < NU + BD) {
-      w.g[(size_t)c * BD + threadIdx.x - NU] = tot;
+    for (int sp = 0; sp < split; ++sp) tot += w.cam_split[((size_t)c * kCamSplitMax + sp) * kCamNV + threadIdx.x];
+    if (MODE == 0) {
+      double* U = w.U + (size_t)c * BD * BD;
+      if (threadIdx.x < NU) {
+        int i = 0, rem = threadIdx.x;
+        while (rem >= BD - i) { rem -= BD - i; ++i; }
+        const int k = i + rem;
+        U[i * BD + k] = tot;
+        U[k * BD + i] = tot;
+      } else if (threadIdx.x < NU + BD) {
+        w.g[(size_t)c * BD + threadIdx.x - NU] = tot;
+      } else {
+        w.costc[c] = tot;
+      }
     } else {
-      w.costc[c] = tot;
+      // stored with row stride (1 + kdsh)
+      const int i = threadIdx.x / (1 + KD), m = threadIdx.x - i * (1 + KD);
+      if (m < 1 + kdsh) w.T[((size_t)c * BD + i) * (1 + kdsh) + m] = tot;
     }
-  } else {
-    // stored with row stride (1 + kdsh)
-    const int i = threadIdx.x / (1 + KD), m = threadIdx.x - i * (1 + KD);
-    if (m < 1 + kdsh) w.T[((size_t)c * BD + i) * (1 + kdsh) + m] = tot;
+  }
+  if constexpr (MODE == 0) {
+    if (step_parts <= 0) return;                   // (uniform: the start linearisation, or the separate reduce_step launch)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wavefront drains its stores
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const int ticket = __hip_atomic_fetch_add(&w.ctl->step_arrivals, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = ticket == (int)gridDim.x - 1;
+      if (last) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      red[0][0] = last ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const bool last = red[0][0] != 0.0;
+    __syncthreads();                               // (red is reused by the sums)
+    if (!last) return;
+    reduce_step_body<true>(w, step_parts, d.C, red);
+    if (threadIdx.x == 0) {
+      w.ctl->merged_step_sums += 1;
+      __hip_atomic_store(&w.ctl->step_arrivals, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 
@@ -1827,6 +1888,9 @@ __global__ __launch_bounds__(256) void tile_reduce_kernel(Ws w, int n_red, int C
 template <int KD>
 __global__ __launch_bounds__(64) void assemble_kernel(DevProblem pb, Ws w, const int32_t* __restrict__ tile_desc, int num_tiles,
                                                       int point_parts) {
+  // (fp contraction off: tile_assemble_kernel computes the same bits, so where a product is fused into an addition is written
+  //  down in both -- fma() below -- and not left to the optimiser)
+#pragma clang fp contract(off)
   constexpr int BD = 6 + KD;
   __shared__ double rz[6][3];
   __shared__ double rzf[BD];                       // tile_rhs with full factors (per-camera intrinsics): BD rows, scaled and masked
@@ -1878,7 +1942,7 @@ __global__ __launch_bounds__(64) void assemble_kernel(DevProblem pb, Ws w, const
         v = w.scale_c[ri] * w.scale_c[cj] * U[i * BD + j];
         if (ri == cj) v += w.dsq_c[ri];
       }
-      if (d.shared && i >= 6) v += w.scale_c[cj] * Tc(j, 1 + (i - 6));   // -F_pose^T E M
+      if (d.shared && i >= 6) v = fma(w.scale_c[cj], Tc(j, 1 + (i - 6)), v);   // -F_pose^T E M
       w.S[(size_t)ri * n + cj] += v;
     }
     if (full) {
@@ -1888,8 +1952,8 @@ __global__ __launch_bounds__(64) void assemble_kernel(DevProblem pb, Ws w, const
         w.rhs[ri] += w.active[ri] ? v : 0.0;
       }
     } else {
-      if (tid < 6) w.rhs[6 * c + tid] += w.scale_c[6 * c + tid] * Tc(tid, 0);
-      if (!trhs && !d.shared && tid >= 6 && tid < BD) w.rhs[ia + tid - 6] += w.scale_c[ia + tid - 6] * T[tid * tw];
+      if (tid < 6) w.rhs[6 * c + tid] = fma(w.scale_c[6 * c + tid], Tc(tid, 0), w.rhs[6 * c + tid]);
+      if (!trhs && !d.shared && tid >= 6 && tid < BD) w.rhs[ia + tid - 6] = fma(w.scale_c[ia + tid - 6], T[tid * tw], w.rhs[ia + tid - 6]);
     }
   } else {
     if (trhs) {                                    // (rides along: max of the point passes' per-workgroup gradient norms,
@@ -1915,7 +1979,7 @@ __global__ __launch_bounds__(64) void assemble_kernel(DevProblem pb, Ws w, const
 #pragma unroll
           for (int j = 0; j <= i; ++j) {
             double v = trhs ? 0.0 : w.scale_c[ia + i] * w.T[((size_t)cc * BD + 6 + i) * tw + 1 + j];
-            if (global_terms) v += w.scale_c[ia + i] * w.scale_c[ia + j] * w.U[(size_t)cc * BD * BD + (6 + i) * BD + 6 + j];
+            if (global_terms) v = fma(w.scale_c[ia + i] * w.scale_c[ia + j], w.U[(size_t)cc * BD * BD + (6 + i) * BD + 6 + j], v);
             sums[i * KD + j] += v;
           }
           sums[KD * KD + i] += trhs ? (global_terms ? w.g[(size_t)cc * BD + 6 + i] : 0.0) : w.T[((size_t)cc * BD + 6 + i) * tw];
@@ -1929,7 +1993,7 @@ __global__ __launch_bounds__(64) void assemble_kernel(DevProblem pb, Ws w, const
 #pragma unroll
           for (int i = 0; i < KD; ++i) {
 #pragma unroll
-            for (int j = 0; j <= i; ++j) sums[i * KD + j] -= w.scale_c[ia + i] * q[KD + i * KD + j];
+            for (int j = 0; j <= i; ++j) sums[i * KD + j] = fma(-w.scale_c[ia + i], q[KD + i * KD + j], sums[i * KD + j]);
             sums[KD * KD + i] -= q[i];
           }
         }
@@ -1945,11 +2009,231 @@ __global__ __launch_bounds__(64) void assemble_kernel(DevProblem pb, Ws w, const
             if (global_terms && i == j) v += w.dsq_c[ia + i];
             w.S[(size_t)(ia + i) * n + ia + j] += v;
           }
-          w.rhs[ia + i] += w.scale_c[ia + i] * sums[KD * KD + i];
+          w.rhs[ia + i] = fma(w.scale_c[ia + i], sums[KD * KD + i], w.rhs[ia + i]);
         }
       }
     }
   }
+}
+
+// LM damping of reduced column j for the current radius (prep_kernel's loop body)
+__device__ __forceinline__ double lm_damping(double colsq, double sc, double radius, const vgg_ba_options& opt) {
+  double dd = colsq * sc * sc;
+  dd = fmin(fmax(dd, opt.min_lm_diagonal), opt.max_lm_diagonal);
+  return dd / radius;
+}
+
+// tile_reduce_kernel + assemble_kernel + prep_kernel in ONE launch (phase 1 with tile_rhs, one tile batch, every camera group
+// with a diagonal tile; the three kernels stay for every other configuration and for vgg_ba_set_tile_rhs(| 4)).  assemble_kernel
+// adds per-camera terms to elements that tile_reduce_kernel stored a few microseconds earlier and derives the right-hand side
+// from the rz sums of the same launch: here the thread that sums an element of a camera's own block adds that camera's term
+// and stores once, and the thread that sums an rz element writes the row of rhs / of the shared-intrinsics border made from it.
+// KD: intrinsics unknowns per block; BD: rows of a tile block (6 = compressed factors: shared or constant intrinsics).
+// grid = (tile_reduce_kernel's x, 1 + num_tiles): row y > 0 is tile y - 1; row 0 carries the two workgroups that need no tile sum,
+//   x = 0: assemble_kernel's extra workgroup (gmax_pts; the shared-intrinsics block from part_Q and the per-camera parts),
+//   x = 1: prep_body (column norms, gmax_cams) when a new linearisation is in place.  The FIRST linearisation's prep_body also
+//          makes scale_c, which point_pass reads: that one stays prep_kernel, a launch in front of point_pass (phase_schur).
+// dsq_c is computed where it is added, from U's diagonal (= colsq_c: prep_body copies it from there) -- and stored as well.
+// Same sums in the same order as the three kernels, so the same bits: fp contraction is OFF in this function and the two
+// places where the compiler contracts assemble_kernel's expressions are spelled fma() -- S = v; S += t rounds v and t first.
+template <int KD, int BD>
+__global__ __launch_bounds__(256) void tile_assemble_kernel(DevProblem pb, Ws w, vgg_ba_options opt,
+                                                            const int32_t* __restrict__ tile_desc, int point_parts) {
+#pragma clang fp contract(off)
+  constexpr int R = kGroup * BD, UBD = 6 + KD;
+  constexpr bool SH = (KD > 0 && BD == 6);          // shared intrinsics: border rows 6 C .. behind the poses
+  constexpr int nb2 = (R * R + 255) / 256;
+  static_assert(BD == 6 || 2 * R <= 256, "the two entry pairs of a full-factor rz row meet in one workgroup");
+  __shared__ double red[256];
+  const Ctl* ctl = w.ctl;
+  if (ctl->done) return;
+  const Dims& d = pb.d;
+  const int C = d.C, n = d.n_red, tid = threadIdx.x;
+  const int global_terms = (ctl->rank == 0);
+  const double radius = ctl->radius;
+  if (blockIdx.y == 0) {
+    if (blockIdx.x == 1) {
+      if (ctl->need_lin && ctl->scale_ready) prep_body<KD>(pb, w, opt, red);   // (uniform branch: the body synchronises)
+      return;
+    }
+    if (blockIdx.x != 0) return;
+    // the shared column norms: prep_body's sum over the cameras, same order (its workgroup may not have stored it yet)
+    double cs[KD > 0 ? KD : 1] = {};
+    if constexpr (SH) {
+      double part[KD];
+#pragma unroll
+      for (int k = 0; k < KD; ++k) part[k] = 0.0;
+      for (int c = tid; c < C; c += 256) {
+#pragma unroll
+        for (int k = 0; k < KD; ++k) part[k] += w.U[(size_t)c * UBD * UBD + (6 + k) * UBD + 6 + k];
+      }
+      const int wv = tid >> 6, ln = tid & 63;
+#pragma unroll
+      for (int k = 0; k < KD; ++k) {
+        const double v = wave_sum(part[k]);
+        if (ln == 0) red[wv * 8 + 1 + k] = v;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < KD; ++k) cs[k] = (red[1 + k] + red[9 + k]) + (red[17 + k] + red[25 + k]);
+    }
+    if (tid >= 64) return;
+    {
+      double m = 0;                                // (one wavefront, round trips to memory: unrolled, see assemble_kernel)
+#pragma unroll 8
+      for (int i = tid; i < point_parts; i += 64) m = fmax(m, w.part_B[i]);
+      m = wave_max(m);
+      if (tid == 0) { w.gmax_pts[0] = m; w.ctl->merged_glue_launches += 1; }
+    }
+    if constexpr (SH) {
+      const int ia = 6 * C;
+      constexpr int NS = KD * KD + KD;
+      double sums[NS];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) sums[i] = 0.0;
+#pragma unroll 4
+      for (int cc = tid; cc < C; cc += 64) {
+#pragma unroll
+        for (int i = 0; i < KD; ++i) {
+#pragma unroll
+          for (int j = 0; j <= i; ++j) {
+            double v = 0.0;
+            if (global_terms) v += w.scale_c[ia + i] * w.scale_c[ia + j] * w.U[(size_t)cc * UBD * UBD + (6 + i) * UBD + 6 + j];
+            sums[i * KD + j] += v;
+          }
+          sums[KD * KD + i] += global_terms ? w.g[(size_t)cc * UBD + 6 + i] : 0.0;
+        }
+      }
+#pragma unroll 8
+      for (int b = tid; b < point_parts; b += 64) {
+        const double* q = w.part_Q + 8 * (size_t)b;
+#pragma unroll
+        for (int i = 0; i < KD; ++i) {
+#pragma unroll
+          for (int j = 0; j <= i; ++j) sums[i * KD + j] = fma(-w.scale_c[ia + i], q[KD + i * KD + j], sums[i * KD + j]);
+          sums[KD * KD + i] -= q[i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NS; ++i) sums[i] = wave_sum(sums[i]);
+      if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < KD; ++i) {
+          const double dsq = lm_damping(cs[i], w.scale_c[ia + i], radius, opt);
+          w.dsq_c[ia + i] = dsq;
+#pragma unroll
+          for (int j = 0; j <= i; ++j) {
+            double v = sums[i * KD + j];
+            if (global_terms && i == j) v += dsq;
+            w.S[(size_t)(ia + i) * n + ia + j] = 0.0 + v;
+          }
+          w.rhs[ia + i] = fma(w.scale_c[ia + i], sums[KD * KD + i], 0.0);
+        }
+      }
+    }
+    return;
+  }
+  const int tile = blockIdx.y - 1;
+  const int gI = tile_desc[4 * tile], gJ = tile_desc[4 * tile + 1];
+  const int c0 = tile_desc[4 * tile + 2], c1 = tile_desc[4 * tile + 3];
+  if ((int)blockIdx.x >= nb2) {
+    // the right-hand-side sums of a diagonal tile (tile_reduce_kernel), then what assemble_kernel makes of them
+    if (gI != gJ) return;
+    constexpr int NE = (BD == 6) ? R * 3 : 2 * R;              // elements, and the chunk stride
+    constexpr size_t STR = (BD == 6) ? (size_t)R * 3 : (size_t)kGroup * 18;
+    const int e = ((int)blockIdx.x - nb2) * 256 + tid;
+    if (BD == 6 && e >= NE) return;
+    const bool live = e < NE;
+    double s0 = 0.0, s1 = 0.0;
+    int ch = c0;
+    const double* src = w.rz_part + (live ? e : 0);            // (a thread beyond the row walks element 0: loads stay unconditional)
+    for (; ch + 7 < c1; ch += 8) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(ch + u) * STR];
+#pragma unroll
+      for (int u = 0; u < 8; u += 2) { s0 += v[u]; s1 += v[u + 1]; }
+    }
+    for (; ch + 1 < c1; ch += 2) { s0 += src[(size_t)ch * STR]; s1 += src[(size_t)(ch + 1) * STR]; }
+    if (ch < c1) s0 += src[(size_t)ch * STR];
+    const double rzv = s0 + s1;
+    if (live) w.rz[(size_t)gI * STR + e] = rzv;
+    if constexpr (BD == 6) {
+      // compressed factors: element (camera slot a, pose row i, column col) -- column 0 is the right-hand side, 1 + k the border
+      // of shared intrinsics k; rz carries neither scales nor masks
+      const int a = e / 18, i = (e - 18 * a) / 3, col = e - 18 * a - 3 * i;
+      const int c = gI * kGroup + a;
+      if (c >= C) return;
+      const int rj = 6 * c + i;
+      const bool act = w.active[rj] != 0;
+      const double sc = w.scale_c[rj];
+      if (col == 0) {
+        const double Tc = act ? ((global_terms ? w.g[(size_t)c * UBD + i] : 0.0) - rzv) : 0.0;
+        w.rhs[rj] = fma(sc, Tc, 0.0);
+      } else if (SH && col <= KD) {
+        const int k = col - 1, ia = 6 * C;
+        double v = 0.0;
+        if (global_terms) v = w.scale_c[ia + k] * sc * w.U[(size_t)c * UBD * UBD + (6 + k) * UBD + i];
+        const double Tc = act ? (0.0 - rzv) : 0.0;
+        v = fma(sc, Tc, v);
+        w.S[(size_t)(ia + k) * n + rj] = 0.0 + v;
+      }
+    } else {
+      // full factors: rz carries scales and masks; a row is the sum of the batch's two entry pairs (elements e and e + R)
+      red[tid] = rzv;
+      __syncthreads();
+      if (e >= R) return;
+      const int a = e / BD, t = e - a * BD;
+      const int c = gI * kGroup + a;
+      if (c >= C) return;
+      const double rzf = red[e] + red[e + R];
+      const int ri = (t < 6) ? 6 * c + t : 6 * C + KD * c + (t - 6);
+      const double v = (global_terms ? w.scale_c[ri] * w.g[(size_t)c * UBD + t] : 0.0) - rzf;
+      w.rhs[ri] = 0.0 + (w.active[ri] ? v : 0.0);
+    }
+    return;
+  }
+  const int e = blockIdx.x * 256 + tid;
+  if (e >= R * R) return;
+  const int row = e / R, col = e - row * R;
+  const int a = row / BD, i = row - a * BD, b = col / BD, j = col - b * BD;
+  const int ca = gI * kGroup + a, cb = gJ * kGroup + b;
+  if (ca >= C || cb >= C) return;
+  if (gI == gJ && col > row) return;             // diagonal tile is symmetric: the lower half is the unique source
+  const int ri = (i < 6) ? 6 * ca + i : 6 * C + KD * ca + (i - 6);
+  const int cj = (j < 6) ? 6 * cb + j : 6 * C + KD * cb + (j - 6);
+  // (eight loads in flight per thread; the order of the additions -- even chunks into s0, odd ones into s1 -- is fixed)
+  double s0 = 0.0, s1 = 0.0;
+  int ch = c0;
+  const double* src = w.tile_part + e;
+  for (; ch + 7 < c1; ch += 8) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(ch + u) * R * R];
+#pragma unroll
+    for (int u = 0; u < 8; u += 2) { s0 += v[u]; s1 += v[u + 1]; }
+  }
+  for (; ch + 1 < c1; ch += 2) { s0 += src[(size_t)ch * R * R]; s1 += src[(size_t)(ch + 1) * R * R]; }
+  if (ch < c1) s0 += src[(size_t)ch * R * R];
+  const int hi = ri > cj ? ri : cj, lo = ri > cj ? cj : ri;
+  double v = -(s0 + s1);
+  if constexpr (BD == 6) {
+    const double mi = w.active[ri] ? w.scale_c[ri] : 0.0, mj = w.active[cj] ? w.scale_c[cj] : 0.0;
+    v *= mi * mj;
+  }
+  if (gI == gJ && a == b) {
+    // the camera's own block (ri >= cj): + s_i s_j U_ij, + the damping on the diagonal -- rank 0 only, the other ranks' share is 0
+    const double* U = w.U + (size_t)ca * UBD * UBD;
+    double t = 0.0;
+    if (global_terms) t = w.scale_c[ri] * w.scale_c[cj] * U[i * UBD + j];
+    if (ri == cj) {
+      const double dsq = lm_damping(U[i * UBD + i], w.scale_c[ri], radius, opt);
+      w.dsq_c[ri] = dsq;
+      if (global_terms) t += dsq;
+    }
+    v = v + t;
+  }
+  w.S[(size_t)hi * n + lo] = v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2129,21 +2413,12 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
   if (threadIdx.x < 3) w.part_F[4 * blockIdx.x + 1 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// reduce buffer 3: [0] the candidate's cost (sum over the cameras of cam_pass<CAND>'s sums), [1..3] the point_step sums
+// (a launch of its own with the separate glue launches, vgg_ba_set_tile_rhs(| 4); otherwise the last workgroup of
+//  cam_reduce_kernel<KD, 0> runs the body)
 __global__ __launch_bounds__(256) void reduce_step_kernel(Ws w, int nparts, int C) {
   __shared__ double red[4][256];
   if (w.ctl->done) return;
-  double s[4] = {0, 0, 0, 0};
-  for (int i = threadIdx.x; i < C; i += 256) s[0] += w.cost_cand[i];
-  for (int i = threadIdx.x; i < nparts; i += 256)
-    for (int k = 1; k < 4; ++k) s[k] += w.part_F[4 * i + k];
-  for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st) for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) w.stepsum[threadIdx.x] = red[threadIdx.x][0];
+  reduce_step_body<false>(w, nparts, C, red);
 }
 
 // Ceres' trust-region decision (TrustRegionMinimizer::Minimize body + LevenbergMarquardtStrategy)
@@ -2410,16 +2685,18 @@ static inline int cam_split_for(int C, int O) {
 // into reduce buffer 0 (vgg_ba_begin), the candidate into lin_cand (phase 2).  One kernel pair for both, so that the
 // linearisation an accepted candidate leaves behind is bit for bit the one a pass at the new x would compute.
 template <int KD>
-static void launch_linearize(const Launch& L, const DevProblem& dp, const Ws& w) {
+static void launch_linearize(const Launch& L, const DevProblem& dp, const Ws& w, int step_parts = 0) {
+  // step_parts > 0: the last workgroup of cam_reduce also sums reduce buffer 3 (the candidate of phase 2)
   const int split = cam_split_for(L.d.C, L.d.O);
   cam_pass_kernel<KD, 0><<<dim3(L.d.C, split), 256, 0, L.st>>>(dp, w);
-  cam_reduce_kernel<KD, 0><<<L.d.C, 64, 0, L.st>>>(dp, w, split, 0);
+  cam_reduce_kernel<KD, 0><<<L.d.C, 256, 0, L.st>>>(dp, w, split, 0, step_parts);
 }
 
 // one batch of Schur tiles: the off-diagonal launch, the diagonal launch, and the ordered sum of their chunks into
 // dst (S, or S2 for a batch that runs beside the factorisation)
 template <int BD>
-static void launch_schur_batch(const Launch& L, int batch, hipStream_t st, double* dst, int which = 0) {
+static void launch_schur_batch(const Launch& L, int batch, hipStream_t st, double* dst, int which = 0, bool sums = true) {
+  // sums = false: the caller sums the chunks itself (tile_assemble_kernel)
   // which: 0 = the whole batch; 1 = the off-diagonal launch and the sums of its tiles; 2 = the diagonal launch and its sums
   // (1 / 2: the split exchange of the sharded solve; never with the merged launch)
   const int32_t* B = L.batches + 6 * batch;
@@ -2435,17 +2712,17 @@ static void launch_schur_batch(const Launch& L, int batch, hipStream_t st, doubl
     ProfScope ps(kProfSchurTileDiag, st);
     schur_tile_kernel<BD, true><<<c1 - cm, 256, 0, st>>>(L.w, L.chunk_desc, L.entries, cm, L.num_segments);
   }
-  if (t1 > t0)
+  if (t1 > t0 && sums)
     tile_reduce_kernel<BD><<<dim3(div_up(kGroup * BD * kGroup * BD, 256) + (L.w.tile_rhs ? (BD == 6 ? div_up(kGroup * BD * 3, 256) : div_up(2 * kGroup * BD, 256)) : 0),
                                   t1 - t0), 256, 0, st>>>(L.w, L.d.n_red, L.d.C, L.d.kd, L.tile_desc, t0, dst, which == 0 ? -1 : which - 1);
 }
 
 template <int KD>
 static void launch_schur_batches(const Launch& L, int b0, int b1, hipStream_t st, double* dst, int32_t* done_flags = nullptr,
-                                 int which = 0) {
+                                 int which = 0, bool sums = true) {
   for (int b = b0; b < b1; ++b) {
-    if (L.d.shared || KD == 0) launch_schur_batch<6>(L, b, st, dst, which);
-    else launch_schur_batch<6 + KD>(L, b, st, dst, which);
+    if (L.d.shared || KD == 0) launch_schur_batch<6>(L, b, st, dst, which, sums);
+    else launch_schur_batch<6 + KD>(L, b, st, dst, which, sums);
     if (done_flags) dataflow_signal(done_flags + b, st);    // (the single-launch factorisation waits on the device)
   }
 }
@@ -2485,6 +2762,51 @@ static OverlapCtx* overlap_ctx(const Launch& L) {
   return &c;
 }
 
+// What the host remembers about a solve between vgg_ba_begin and its phases, by workspace: whether prep_kernel still has to run
+// in front of point_pass (the first linearisation: it makes scale_c), and whether every camera group has a diagonal tile
+// (tile_assemble_kernel's threads are the tiles' elements: a group without observations has nobody to add its cameras' terms).
+// A workspace the table does not know -- more than kHostSolves solves begun since -- takes the separate launches.
+struct HostSolve { const void* ws; bool prep_pending, all_diag; };
+constexpr int kHostSolves = 64;
+static HostSolve g_host_solves[kHostSolves];
+static int g_host_solve_next = 0;
+static std::mutex g_host_solve_mutex;
+
+static void host_solve_begin(const void* ws, bool all_diag) {
+  std::lock_guard<std::mutex> lock(g_host_solve_mutex);
+  HostSolve* h = nullptr;
+  for (HostSolve& e : g_host_solves) if (e.ws == ws) h = &e;
+  if (!h) { h = &g_host_solves[g_host_solve_next]; g_host_solve_next = (g_host_solve_next + 1) % kHostSolves; }
+  *h = HostSolve{ws, true, all_diag};
+}
+// the entry's state; *prep_pending is handed out once
+static bool host_solve_state(const void* ws, bool* prep_pending, bool* all_diag) {
+  std::lock_guard<std::mutex> lock(g_host_solve_mutex);
+  for (HostSolve& e : g_host_solves) {
+    if (e.ws != ws || !ws) continue;
+    *prep_pending = e.prep_pending; *all_diag = e.all_diag;
+    e.prep_pending = false;
+    return true;
+  }
+  return false;
+}
+
+// one copy of the tile table to the host per solve (a few hundred tiles at most), in stream order behind its upload
+static bool every_group_has_diagonal_tile(const Launch& L) {
+  const int G = div_up(L.d.C, kGroup);
+  if (!L.tile_desc || L.num_tiles < G) return false;
+  std::vector<int32_t> td((size_t)4 * L.num_tiles);
+  if (hipMemcpyAsync(td.data(), L.tile_desc, sizeof(int32_t) * td.size(), hipMemcpyDeviceToHost, L.st) != hipSuccess ||
+      hipStreamSynchronize(L.st) != hipSuccess) { (void)hipGetLastError(); return false; }
+  std::vector<char> seen((size_t)G, 0);
+  for (int t = 0; t < L.num_tiles; ++t) {
+    const int gI = td[4 * t], gJ = td[4 * t + 1];
+    if (gI == gJ && gI >= 0 && gI < G && td[4 * t + 3] > td[4 * t + 2]) seen[gI] = 1;
+  }
+  for (char c : seen) if (!c) return false;
+  return true;
+}
+
 // which: 0 = the whole phase; 1 = up to the off-diagonal tile launch and the sums of its tiles; 2 = the diagonal launch, its
 // sums and assemble (1 / 2: the split exchange of the sharded solve, phases 7 / 9 -- one tile batch, separate launches)
 template <int KD>
@@ -2495,7 +2817,13 @@ static void phase_schur(const Launch& L, int which = 0) {
     assemble_kernel<KD><<<d.C + 1, 64, 0, L.st>>>(L.dp, L.w, L.tile_desc, L.num_tiles, L.wgB);
     return;
   }
-  prep_kernel<KD><<<1, 256, 0, L.st>>>(L.dp, L.w, L.opt);
+  // one launch for the tile sums, assembly and preparation (tile_assemble_kernel) where its conditions hold; then prep_kernel
+  // runs only in front of the first point_pass of a solve
+  bool prep_pending = true, all_diag = false;
+  const bool known = host_solve_state(L.w.ctl, &prep_pending, &all_diag);
+  const bool fused = which == 0 && known && all_diag && !g_tuning.legacy_glue && L.w.tile_rhs && L.num_chunks > 0 &&
+                     L.num_batches == 1 && L.batches[3] == 0 && L.batches[4] == L.num_tiles;
+  if (!fused || prep_pending) prep_kernel<KD><<<1, 256, 0, L.st>>>(L.dp, L.w, L.opt);
   {
     ProfScope ps(kProfPointPass, L.st);
     // cameras (q, t, pose scales, constant flags: 14 doubles each) cached in LDS when they fit beside 2 workgroups/CU
@@ -2529,7 +2857,7 @@ static void phase_schur(const Launch& L, int which = 0) {
     ProfScope ps(kProfCamRhs, L.st);
     const int split = cam_split_for(d.C, d.O);
     cam_pass_kernel<KD, 1><<<dim3(d.C, split), 256, 0, L.st>>>(L.dp, L.w);
-    cam_reduce_kernel<KD, 1><<<d.C, 64, 0, L.st>>>(L.dp, L.w, split, L.wgB);
+    cam_reduce_kernel<KD, 1><<<d.C, 64, 0, L.st>>>(L.dp, L.w, split, L.wgB, 0);
   }
   // (the reduced system was zeroed by cam_pass_kernel<KD, 1>: no fill launch)
   if (which == 1) {
@@ -2542,8 +2870,19 @@ static void phase_schur(const Launch& L, int which = 0) {
       (void)hipMemsetAsync(L.w.S2, 0, sizeof(double) * (size_t)d.n_red * d.n_red, L.st);
       launch_schur_batches<KD>(L, 0, 1, L.st, L.w.S);
     } else {
-      launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S);
+      launch_schur_batches<KD>(L, 0, L.num_batches, L.st, L.w.S, nullptr, 0, !fused);
     }
+  }
+  if (fused) {
+    auto launch = [&](auto bd) {
+      constexpr int BD = decltype(bd)::value;
+      constexpr int R = kGroup * BD;
+      const int gx = div_up(R * R, 256) + (BD == 6 ? div_up(R * 3, 256) : div_up(2 * R, 256));
+      tile_assemble_kernel<KD, BD><<<dim3(gx, 1 + L.num_tiles), 256, 0, L.st>>>(L.dp, L.w, L.opt, L.tile_desc, L.wgB);
+    };
+    if (d.shared || KD == 0) launch(std::integral_constant<int, 6>{});
+    else launch(std::integral_constant<int, 6 + KD>{});
+    return;
   }
   assemble_kernel<KD><<<d.C + 1, 64, 0, L.st>>>(L.dp, L.w, L.tile_desc, L.num_tiles, L.wgB);
 }
@@ -2605,9 +2944,9 @@ static int phase_step(const Launch& L) {
     dc.cam_q = L.w.cand_q; dc.cam_t = L.w.cand_t; dc.intr = L.w.cand_intr; dc.pts = L.w.cand_pts;
     Ws wc = L.w;
     wc.U = L.w.U_cand; wc.g = L.w.g_cand; wc.costc = L.w.cost_cand;
-    launch_linearize<KD>(L, dc, wc);
+    launch_linearize<KD>(L, dc, wc, g_tuning.legacy_glue ? 0 : L.wgB);
   }
-  reduce_step_kernel<<<1, 256, 0, L.st>>>(L.w, L.wgB, d.C);
+  if (g_tuning.legacy_glue) reduce_step_kernel<<<1, 256, 0, L.st>>>(L.w, L.wgB, d.C);
   return VGG_OK;
 }
 
@@ -2746,12 +3085,15 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
   if (!(lanes_per_point == 0 || lanes_per_point == 8 || lanes_per_point == 16 || lanes_per_point == 32 || lanes_per_point == 64))
     return VGG_ERR_INVALID_ARGUMENT;
   vgg::g_tuning = vgg::Tuning{lanes_per_point, long_tracks < 0 ? -1 : (long_tracks ? 1 : 0), cam_workgroups > 0 ? cam_workgroups : 0,
-                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs};
+                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs, vgg::g_tuning.legacy_glue};
   return VGG_OK;
 }
 
 int vgg_ba_set_tile_rhs(int enable) {
-  vgg::g_tuning.tile_rhs = (enable >= 0 && enable <= 2) ? enable : 1;
+  // bits 0..1: 0 / 1 / 2 as include/vggsfm_amd.h describes them; bit 2: keep the separate glue launches
+  const bool known = enable >= 0 && enable <= 7 && (enable & 3) <= 2;
+  vgg::g_tuning.tile_rhs = known ? (enable & 3) : 1;
+  vgg::g_tuning.legacy_glue = (known && (enable & 4)) ? 1 : 0;
   return VGG_OK;
 }
 
@@ -2815,6 +3157,7 @@ int vgg_ba_begin(const vgg_ba_problem* problem, const vgg_ba_options* options, v
   if (rc != VGG_OK) return rc;
   if (workspace_bytes < L.w.total_bytes) return VGG_ERR_WORKSPACE;
   if (world_size < 1 || world_size > kPackPad || rank < 0 || rank >= world_size) return VGG_ERR_INVALID_ARGUMENT;
+  host_solve_begin(L.w.ctl, L.w.tile_rhs && !g_tuning.legacy_glue && every_group_has_diagonal_tile(L));
   VGG_HIP_CHECK(hipMemsetAsync(L.w.Y, 0, L.w.y_bytes, L.st));   // absent slots stay zero for the whole solve
   // the whole S | rhs once: the phases clear and fill only the lower triangle (zero_system_lower), and nothing writes the
   // strict upper one, so it stays zero -- reduce buffer 1 as include/vggsfm_amd.h describes it
