@@ -227,6 +227,11 @@ int vgg_ba_solve(const vgg_ba_problem* problem, const vgg_ba_options* options, v
  *   phase 0 LINEARIZE: launches nothing: reduce buffer 0 holds the local camera-side terms of the current x    -> SUM
  *   phase 1 SCHUR    : point blocks, reduced camera system of the local points -> reduce buffer 1 (SUM),
  *                      gradient max of local points                            -> reduce buffer 2 (MAX)
+ *                      (buffer 1 = S | rhs of  S y = rhs,  S = A_cc - sum_p W_p V_p^-1 W_p^T,  rhs = + J_c^T r - sum_p W_p V_p^-1
+ *                      J_p^T r  in Jacobi-scaled columns, damping included, lower triangle; the step is -y o scale.  An inactive
+ *                      column j -- constant, or of a frame without observations -- holds the damping of a zero column,
+ *                      min_lm_diagonal / radius, at S[j][j] on rank 0 and zeros elsewhere in its row, its column and rhs[j];
+ *                      phase 2 puts the unit diagonal there after the sum.  tests/test_gpu_ba_system.py)
  *   phase 2 STEP     : Cholesky + back-substitution, then the camera-side pass at the candidate: its local cost, the
  *                      model cost change and the step norms                    -> reduce buffer 3 (SUM); its local
  *                      J^T J / J^T r / cost are kept in the workspace (not a reduce buffer)

@@ -144,8 +144,11 @@ class _Problem:
         r = self._res(*self._gather(q, t, intr, X))
         return 0.5 * float(_rho(self.loss, self.loss_scale, (r * r).sum(1)).sum())
 
-    def linearize(self, q, t, intr, X):
-        """-> cost, corrected residual (2O,), corrected dense Jacobian (2O, n) with constant columns zero."""
+    def blocks(self, q, t, intr, X):
+        """-> cost, corrected residuals (O,2), F (O,2,6+kd), E (O,2,3), cols (O,6+kd): the per-observation Jacobian blocks
+        with respect to the observation's camera columns (pose tangent, then its intrinsics block's refined parameters;
+        `cols` = their indices in the tangent layout) and to its point (columns n_red + 3 obs_pt + 0..2), constant and
+        unobserved columns zero.  What `linearize` scatters into the dense matrix -- for problems too large for that."""
         args = self._gather(q, t, intr, X)
         r = self._res(*args)
         Jq, Jt, Jfk, JX = self._jac(*args)
@@ -153,19 +156,26 @@ class _Problem:
         rho = _rho(self.loss, self.loss_scale, s)
         (rho1,) = torch.autograd.grad(rho.sum(), s)
         w = torch.sqrt(rho1.detach())                     # Triggs correction with rho'' <= 0: sqrt(rho') only
+        F = torch.cat([Jq, Jt, Jfk[:, :, self.kcols]], 2) * w[:, None, None]
+        E = (JX * w[:, None, None]).numpy().copy()
+        F = F.numpy().copy()
+        cols = np.concatenate([6 * self.obs_cam[:, None] + np.arange(6)[None],
+                               6 * self.C + self.kd * self.cam_intr[self.obs_cam][:, None] + np.arange(self.kd)[None]], 1)
+        F *= self.active[cols][:, None, :]
+        E *= self.active[self.n_red + 3 * self.obs_pt][:, None, None]      # (a point's three columns are active together)
+        return 0.5 * float(rho.detach().sum()), (w[:, None] * r).numpy(), F, E, cols
+
+    def linearize(self, q, t, intr, X):
+        """-> cost, corrected residual (2O,), corrected dense Jacobian (2O, n) with constant columns zero."""
+        cost, r, F, E, cols = self.blocks(q, t, intr, X)
         O = len(self.obs_cam)
         J = np.zeros((O, 2, self.n))
         idx = np.arange(O)
+        for k in range(cols.shape[1]):
+            J[idx, :, cols[:, k]] = F[:, :, k]
         for k in range(3):
-            J[idx, :, 6 * self.obs_cam + k] = (w[:, None] * Jq[:, :, k]).numpy()
-            J[idx, :, 6 * self.obs_cam + 3 + k] = (w[:, None] * Jt[:, :, k]).numpy()
-            J[idx, :, self.n_red + 3 * self.obs_pt + k] = (w[:, None] * JX[:, :, k]).numpy()
-        ic = 6 * self.C + self.kd * self.cam_intr[self.obs_cam]
-        for j, src in enumerate(self.kcols):
-            J[idx, :, ic + j] = (w[:, None] * Jfk[:, :, src]).numpy()
-        J = J.reshape(2 * O, self.n)
-        J[:, ~self.active] = 0.0
-        return 0.5 * float(rho.detach().sum()), (w[:, None] * r).numpy().reshape(-1), J
+            J[idx, :, self.n_red + 3 * self.obs_pt + k] = E[:, :, k]
+        return cost, r.reshape(-1), J.reshape(2 * O, self.n)
 
     def plus(self, q, t, intr, X, delta):
         nq = np.stack([_quat_plus_np(q[c], delta[6 * c:6 * c + 3]) for c in range(self.C)])
