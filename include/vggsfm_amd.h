@@ -294,7 +294,8 @@ int vgg_pose_refine(const double* points3D, const void* tracks, int tracks_are_f
  * = COLMAP EstimateAbsolutePose restated (third-party, absent from the reference tree; PARITY UNPINNED, see
  * oracle/p3p.py): P3P minimal samples, squared reprojection error on the normalised image plane, points with
  * depth <= 0 never inliers, support = (most inliers, then smallest inlier residual sum, then lowest index).
- * Deviations: the caller draws a fixed number of samples (no adaptive trial count), no EPnP step inside the loop;
+ * Deviations: the caller draws a fixed number of samples (no adaptive trial count), no EPnP step inside the loop
+ * (the local optimisation is a separate, opt-in entry applied to each frame's winner: vggsfm_amd_pnp.h);
  * the caller runs vgg_pose_refine on the returned inliers afterwards, as COLMAP does.
  * All num_frames (virtual) frames run concurrently.  A virtual frame is (frame, focal length factor): COLMAP's
  * estimate_focal_length runs one RANSAC per factor -- the caller passes the points normalised with each scaled

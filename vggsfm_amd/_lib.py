@@ -9,7 +9,8 @@ loaded: callers pass tensors, ``None``, ints and floats as they are.  A new C-AB
 header and one row in that table (tests/test_host_logic.py compares the two, type by type).  include/vggsfm_amd.h and
 ``SIGNATURES`` are a closed set; the multi-view entries (include/vggsfm_amd_multiview.h, prefix ``vggx_``) have the table
 ``SIGNATURES_MULTIVIEW``, applied next to the first, and the essential-matrix entries (include/vggsfm_amd_essential.h, prefix
-``vgge_emat_``) the table ``SIGNATURES_ESSENTIAL``.
+``vgge_emat_``) the table ``SIGNATURES_ESSENTIAL``, and the EPnP entries (include/vggsfm_amd_pnp.h, prefix ``vggp_``) the table
+``SIGNATURES_PNP``.
 """
 import ctypes
 import operator
@@ -176,6 +177,15 @@ SIGNATURES_ESSENTIAL = {
 }
 EXPORTED_ESSENTIAL = list(SIGNATURES_ESSENTIAL)
 
+# The fourth table: the vggp_* entries of include/vggsfm_amd_pnp.h (csrc/epnp.hip, same library), in that header's order.
+# tests/test_pnp_host.py compares the two.
+SIGNATURES_PNP = {
+    "vggp_epnp_solve": (_INT, [_P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vggp_pose_score": (_INT, [_P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
+    "vggp_epnp_lo": (_INT, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
+}
+EXPORTED_PNP = list(SIGNATURES_PNP)
+
 _lib = None
 
 
@@ -203,7 +213,7 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL):
+    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL, SIGNATURES_PNP):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -47,6 +47,7 @@ class AbsolutePoseRefinementOptions:
 class RANSACOptions:
     max_error: float = 12.0                           # pixels (COLMAP AbsolutePoseEstimationOptions.ransac.max_error default)
     num_hypotheses: int = 1024                        # device path: fixed number of minimal samples (COLMAP: adaptive, <= 10000)
+    lo_max_rounds: int = 0                            # EPnP local optimisation of each virtual frame's winner (COLMAP: 10); 0 = off
 
 
 @dataclass

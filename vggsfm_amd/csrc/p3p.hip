@@ -5,8 +5,11 @@
 // restated from its published behaviour -- minimal P3P samples, squared reprojection error on the normalised image
 // plane, points behind the camera never inliers, support = (most inliers, then smallest inlier residual sum) -- with
 // two documented deviations: a fixed number of hypotheses drawn by the caller (no adaptive trial count; COLMAP's own
-// RNG cannot be reproduced anyway) and no EPnP local optimisation inside the loop (the callers run the non-linear
-// pose refinement on the RANSAC inliers afterwards, as COLMAP does).  oracle/p3p.py mirrors this file operation by
+// RNG cannot be reproduced anyway) and no EPnP local optimisation inside the loop: the samples are all drawn up front, so
+// COLMAP's local step (EPnP on the inliers, up to 10 trials while the support improves) exists as a separate, opt-in
+// entry that is applied to the final best model of each virtual frame, not at each improvement during sampling
+// (epnp.hip, vggp_epnp_lo; RANSACOptions.lo_max_rounds, 0 = off).  The callers run the non-linear pose refinement on
+// the RANSAC inliers afterwards, as COLMAP does.  oracle/p3p.py mirrors this file operation by
 // operation (this file is compiled with -ffp-contract=off), so the two agree bit for bit on the same samples.
 //
 // Minimal solver: ratios u = d2/d1, v = d3/d1 of the three depths; the two distance-ratio equations are quadratics

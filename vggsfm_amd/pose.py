@@ -133,11 +133,78 @@ def p3p_ransac(points2D_normalized, points3D, candidate_mask, samples, max_error
     return pose, num, rsum, best, inl.bool()
 
 
+def _score_shapes(points2D_normalized, points3D, candidate_mask, max_error_sq):
+    if points2D_normalized.dim() != 3 or points2D_normalized.shape[2] != 2 or \
+            tuple(points3D.shape) != (points2D_normalized.shape[1], 3):
+        raise ValueError(f"points2D_normalized must be (F,P,2) and points3D (P,3), got {tuple(points2D_normalized.shape)} "
+                         f"and {tuple(points3D.shape)}")
+    F, P = points2D_normalized.shape[0], points2D_normalized.shape[1]
+    if candidate_mask is not None and tuple(candidate_mask.shape) != (F, P):
+        raise ValueError("candidate_mask must be (F,P)")
+    if tuple(max_error_sq.shape) != (F,):
+        raise ValueError("max_error_sq must be (F,)")
+    return F, P
+
+
+def _score_tensors(points2D_normalized, points3D, candidate_mask, max_error_sq):
+    _lib.require_gpu(points2D_normalized, points3D, candidate_mask, max_error_sq)
+    x = points2D_normalized.to(torch.float64).contiguous()
+    X = points3D.to(torch.float64).contiguous()
+    mk = None if candidate_mask is None else candidate_mask.to(torch.uint8).contiguous()
+    return x, X, mk, max_error_sq.to(torch.float64).contiguous()
+
+
+def pose_score(poses, points2D_normalized, points3D, candidate_mask, max_error_sq, return_masks=False):
+    """Host side of ``vggp_pose_score``: the support of given poses under the rule of ``p3p_ransac``.  poses (F,L,3,4),
+    points2D_normalized (F,P,2), points3D (P,3), candidate_mask (F,P) bool or None, max_error_sq (F,).
+    Returns (num_inliers (F,L) int32, residual_sum (F,L)[, inlier_mask (F,L,P) bool])."""
+    F, P = _score_shapes(points2D_normalized, points3D, candidate_mask, max_error_sq)
+    if poses.dim() != 4 or poses.shape[0] != F or tuple(poses.shape[2:]) != (3, 4) or poses.shape[1] < 1:
+        raise ValueError(f"poses must be (F,L,3,4), got {tuple(poses.shape)}")
+    x, X, mk, thr = _score_tensors(points2D_normalized, points3D, candidate_mask, max_error_sq)
+    _lib.require_gpu(poses)
+    Lp = int(poses.shape[1])
+    dev = X.device
+    ps = poses.to(torch.float64).contiguous()
+    num = torch.empty((F, Lp), dtype=torch.int32, device=dev)
+    rsum = torch.empty((F, Lp), dtype=torch.float64, device=dev)
+    masks = torch.empty((F, Lp, P), dtype=torch.uint8, device=dev) if return_masks else None
+    _lib.check(_lib.lib().vggp_pose_score(ps, x, X, mk, thr, F, Lp, P, num, rsum, masks, _lib.stream_ptr()), "vggp_pose_score")
+    return (num, rsum, masks.bool()) if return_masks else (num, rsum)
+
+
+def epnp_local_optimisation(pose, num_inliers, residual_sum, inlier_mask, points2D_normalized, points3D, candidate_mask,
+                            max_error_sq, max_rounds=10):
+    """Host side of ``vggp_epnp_lo``: the local optimisation of COLMAP's absolute pose LO-RANSAC (EPnP on the inliers while the
+    support improves, up to `max_rounds` times) on the final pose of every (virtual) frame, all frames concurrently.
+    pose (F,3,4), num_inliers (F,) int32, residual_sum (F,), inlier_mask (F,P) bool as ``p3p_ransac`` returns them; the other
+    arguments as for ``pose_score``.  A frame with num_inliers 0 is returned untouched; every other frame gets the support of
+    its pose recomputed, also with max_rounds = 0.  Returns new (pose, num_inliers, residual_sum, inlier_mask)."""
+    F, P = _score_shapes(points2D_normalized, points3D, candidate_mask, max_error_sq)
+    if tuple(pose.shape) != (F, 3, 4) or tuple(num_inliers.shape) != (F,) or tuple(residual_sum.shape) != (F,) or \
+            tuple(inlier_mask.shape) != (F, P):
+        raise ValueError("pose must be (F,3,4), num_inliers and residual_sum (F,), inlier_mask (F,P)")
+    if max_rounds < 0:
+        raise ValueError("max_rounds must be >= 0")
+    if P < 4:
+        raise ValueError(f"need at least 4 points, got {P}")
+    x, X, mk, thr = _score_tensors(points2D_normalized, points3D, candidate_mask, max_error_sq)
+    _lib.require_gpu(pose, num_inliers, residual_sum, inlier_mask)
+    ps = pose.to(torch.float64).contiguous().clone()
+    num = num_inliers.to(torch.int32).contiguous().clone()
+    rsum = residual_sum.to(torch.float64).contiguous().clone()
+    inl = inlier_mask.to(torch.uint8).contiguous().clone()
+    _lib.check(_lib.lib().vggp_epnp_lo(x, X, mk, thr, F, P, int(max_rounds), ps, num, rsum, inl, _lib.stream_ptr()),
+               "vggp_epnp_lo")
+    return ps, num, rsum, inl.bool()
+
+
 def absolute_pose_estimation_batch(extrinsics, intr_params, points2D, points3D, candidate_mask, frame_ids, camera_type,
                                    refine_flags, estoptions=None, refopts=None, generator=None, max_virtual_points=1 << 25):
     """``pycolmap.absolute_pose_estimation`` for the frames in `frame_ids`, all at once: P3P RANSAC over the
-    candidate matches (optionally over COLMAP's 30 focal length factors), then the non-linear pose refinement on the
-    RANSAC inliers (reference call sites: vggsfm/utils/triangulation.py:413-430, video_runner.py:991-998).
+    candidate matches (optionally over COLMAP's 30 focal length factors), with ``estoptions.ransac.lo_max_rounds`` > 0 the
+    EPnP local optimisation of every virtual frame's winner, then the non-linear pose refinement on the RANSAC inliers
+    (reference call sites: vggsfm/utils/triangulation.py:413-430, video_runner.py:991-998).
 
     extrinsics (S,3,4), intr_params (S,4) = (f,cx,cy,k), points2D (S,P,2) pixels, points3D (P,3), candidate_mask (S,P)
     bool (the reference passes ``points2D[mask], points3D[mask]``), refine_flags (S,) uint8 for the refinement.
@@ -181,7 +248,12 @@ def absolute_pose_estimation_batch(extrinsics, intr_params, points2D, points3D, 
         pts2 = points2D[f].repeat_interleave(G, dim=0)
         xn = cam_from_img(pts2, K, extra)
         thr = (float(estoptions.ransac.max_error) / foc) ** 2             # CamFromImgThreshold: max_error / focal
-        pose, num, rsum, _, inl = p3p_ransac(xn, points3D, cand.repeat_interleave(G, dim=0), samples, thr, G)
+        candv = cand.repeat_interleave(G, dim=0)
+        pose, num, rsum, _, inl = p3p_ransac(xn, points3D, candv, samples, thr, G)
+        if estoptions.ransac.lo_max_rounds > 0 and P >= 4:
+            # COLMAP's local optimisation, on the winner of every virtual frame: the choice below sees the optimised supports
+            pose, num, rsum, inl = epnp_local_optimisation(pose, num, rsum, inl, xn, points3D, candv, thr,
+                                                           estoptions.ransac.lo_max_rounds)
         # best factor per frame: most inliers, then the smaller residual sum, then the first factor
         num2, rs2 = num.reshape(Fc, G).long(), rsum.reshape(Fc, G)
         top = num2.max(1).values
