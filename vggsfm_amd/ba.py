@@ -178,7 +178,9 @@ class DeviceProblem:
 # VGGSFM_TILE_FIXED_COST, VGGSFM_TILE_POS_WEIGHT, VGGSFM_SORT_POINTS, VGGSFM_TILE_WGS and VGGSFM_TILE_BACKFILL override the
 # constants below, and VGGSFM_LEGACY_GLUE=1 keeps the separate glue launches of an LM iteration (solve), all read per call
 # (A/B runs switch them in-process).  Every one of them changes the SCHEDULE of the work,
-# never a sum: results are bit-identical across their values (tests/test_gpu_ba.py).
+# never a sum: results are bit-identical across their values (tests/test_gpu_ba.py).  The exception is VGGSFM_LEGACY_STEP=1
+# (solve): the back-substitution sweep over full Jacobians, which rounds the candidate points and the model cost change
+# differently from the directional sweep.
 def _hook(name, default=None):
     if os.environ.get("VGGSFM_AMD_DEBUG_HOOKS") != "1":
         return default
@@ -901,17 +903,22 @@ def _summary_dict(summ, log, n):
                 n_reduced=summ.n_reduced, iterations=its)
 
 
+def apply_launch_hooks(L):
+    """Measurement hooks of a solve (solve, dist.ShardedBA.begin): VGGSFM_LEGACY_GLUE "1" = the separate glue launches, "0" =
+    the merged ones; VGGSFM_LEGACY_STEP "1" = point_step's sweep over full Jacobians, "0" = the directional one.  Either
+    variable, with either value, also sets the right-hand-side mode to 2 (the default): vgg_ba_set_tile_rhs takes all of them in
+    one integer and has no getter, so a harness that chose mode 0 / 1 must set neither (scripts/prof/ab_c3.py does not)."""
+    glue, step = _hook("VGGSFM_LEGACY_GLUE"), _hook("VGGSFM_LEGACY_STEP")
+    if glue is not None or step is not None:
+        L.vgg_ba_set_tile_rhs(2 | (4 if glue == "1" else 0) | (8 if step == "1" else 0))
+
+
 def solve(problem: DeviceProblem, options: Optional[BundleAdjustmentOptions] = None, workspace=None):
     """Run the LM loop of `problem` in place on the current stream.  Host syncs: one at the start (vgg_ba_begin reads the tile
     table, a few KB, to see whether every camera group has a diagonal tile), the `done` poll every eighth iteration, and one
     at the end."""
     L = _lib.lib()
-    # measurement hook: "1" = the separate glue launches, "0" = the merged ones.  Either value also sets the right-hand-side
-    # mode to 2 (the default): vgg_ba_set_tile_rhs takes both in one integer and has no getter, so a harness that chose mode
-    # 0 / 1 must not set this variable (scripts/prof/ab_c3.py does not)
-    glue = _hook("VGGSFM_LEGACY_GLUE")
-    if glue is not None:
-        L.vgg_ba_set_tile_rhs(2 | (4 if glue == "1" else 0))
+    apply_launch_hooks(L)
     options = options or BundleAdjustmentOptions()
     problem.refine_focal = options.refine_focal_length
     problem.refine_extra = options.refine_extra_params

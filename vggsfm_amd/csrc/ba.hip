@@ -92,6 +92,7 @@ struct Ctl {
   int32_t step_arrivals;          // cam_reduce workgroups of the candidate's linearisation that have stored (the last one sums)
   // how often this solve ran the merged glue: tile_assemble_kernel launches, step sums in cam_reduce_kernel (tests read them)
   int32_t merged_glue_launches, merged_step_sums;
+  int32_t fused_step_prologues;   // point_step launches of this solve that ran cam_update's body in their prologue (tests read it)
 };
 
 struct Dims {
@@ -173,8 +174,10 @@ static Dims make_dims(const vgg_ba_problem* pb) {
 // overrides of the automatic launch choices (vgg_ba_tuning, vgg_ba_set_tile_rhs): 0 / -1 = automatic
 // legacy_glue (vgg_ba_set_tile_rhs(| 4), A/B runs and tests): tile sums, assembly, preparation and the step sums as the separate
 // launches they were before they were merged (tile_assemble_kernel, cam_reduce_kernel's last arriver)
-struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs, legacy_glue; };
-static Tuning g_tuning = {0, -1, 0, 0, 2, 0};
+// legacy_step (vgg_ba_set_tile_rhs(| 8), A/B runs): point_step's sweep over full Jacobians with the model cost change summed
+// observation by observation, as before the directional sweep
+struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs, legacy_glue, legacy_step; };
+static Tuning g_tuning = {0, -1, 0, 0, 2, 0, 0};
 
 static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, void* base) {
   Ws w;
@@ -357,6 +360,41 @@ __device__ __forceinline__ void block_sum(double* v, double* lds /* [4][NV] */, 
   __syncthreads();
 }
 
+// The wave sums of block_sum as a reduce-scatter butterfly: the same xor steps in the same order as wave_sum, but at each step
+// a lane keeps one half of its values -- the low half where the step's lane bit is clear, the high half where it is set --
+// and sends the other half, so a step adds ceil(N / 2) values instead of N: 23 + 12 + 6 + 3 + 2 + 1 additions for 45 values
+// instead of 45 x 6.  The pairing tree of every value is wave_sum's (the keeper adds its partner's partial sum to its own,
+// and a + b = b + a), so the sums are wave_sum's to the last bit; value i ends in ONE lane instead of in all.
+// N: values this lane holds (capacity; the last may be padding where an odd count was halved), n: how many of them are real,
+// base: index of v[0] among the NV values.
+template <int N, int OFF>
+__device__ __forceinline__ void wave_reduce_scatter(double* v, int lane, int n, int base, double* dst) {
+  if constexpr (OFF == 0) {
+    static_assert(N == 1, "64 lanes hold at most 64 values");
+    if (n > 0) dst[base] = v[0];
+  } else {
+    constexpr int H = (N + 1) / 2;
+    const bool hi = (lane & OFF) != 0;
+    double k[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+      const double up = (H + i < N) ? v[H + i] : 0.0;
+      const double send = hi ? v[i] : up, keep = hi ? up : v[i];
+      k[i] = keep + __shfl_xor(send, OFF, 64);
+    }
+    wave_reduce_scatter<H, OFF / 2>(k, lane, hi ? max(n - H, 0) : min(n, H), base + (hi ? H : 0), dst);
+  }
+}
+template <int NV>
+__device__ __forceinline__ void block_sum_scatter(double* v, double* lds /* [4][NV] */, double* out /* lds [NV] */) {
+  static_assert(NV <= 64, "one value per lane at the end");
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  wave_reduce_scatter<NV, 32>(v, lane, NV, 0, lds + wave * NV);
+  __syncthreads();
+  if (threadIdx.x < NV) out[threadIdx.x] = lds[threadIdx.x] + lds[NV + threadIdx.x] + lds[2 * NV + threadIdx.x] + lds[3 * NV + threadIdx.x];
+  __syncthreads();
+}
+
 // ---------------------------------------------------------------------------------------------
 __global__ void init_kernel(DevProblem pb, Ws w, vgg_ba_options opt, int rank, int world) {
   const Dims& d = pb.d;
@@ -517,7 +555,8 @@ __global__ __launch_bounds__(256, (MODE == 1) ? VGG_CP_OCC_RHS : VGG_CP_OCC) voi
         for (int m = 0; m < 1 + KD; ++m) acc[i * (1 + KD) + m] += F[i] * R0[m] + F[BD + i] * R1[m];
     }
   }
-  block_sum<NV>(acc, red, tot);
+  if (MODE == 0) block_sum_scatter<NV>(acc, red, tot);
+  else block_sum<NV>(acc, red, tot);
   static_assert(NV <= kCamNV, "cam_split row");
   if (threadIdx.x < NV) w.cam_split[((size_t)c * kCamSplitMax + blockIdx.y) * kCamNV + threadIdx.x] = tot[threadIdx.x];
 }
@@ -2237,61 +2276,120 @@ __global__ __launch_bounds__(256) void tile_assemble_kernel(DevProblem pb, Ws w,
 }
 
 // ---------------------------------------------------------------------------------------------
-// candidate cameras: x (+) (-s o y); also the camera-side part of |step| and |x|
+// candidate cameras: x (+) (-s o y); also the camera-side part of |step| and |x| and, with CAM_MCC, the cameras' share of the
+// model cost change.  One thread per camera c < C and one more (c == C) for a shared intrinsics block.
+//
+// The cameras' share: with m = -(F dy + E ys) the model residual of an observation, the terms of -sum m.(r + m/2) that hold
+// dy alone are sum_obs [F dy . r - |F dy|^2 / 2] (see point_step_kernel).  Summed camera by camera they are
+//   dy_c^T g_c - dy_c^T U_c dy_c / 2,      g_c = sum F^T r,  U_c = sum F^T F  (dy_c: the six pose entries, then the intrinsics')
+// -- the linearisation cam_pass<.,0> stored in reduce buffer 0 at this very point (corrected, constant-masked, unscaled; with
+// several ranks all-reduced, so the share is the same on every rank and control_kernel adds it un-reduced).  A shared
+// intrinsics block enters through every camera's BD x BD block.
 template <int KD>
-__global__ void cam_update_kernel(DevProblem pb, Ws w) {
-  if (w.ctl->done) return;
+__device__ __forceinline__ void cam_update_body(const DevProblem& pb, const Ws& w, int c, bool cam_mcc) {
+  constexpr int BD = 6 + KD;
   const Dims& d = pb.d;
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c > d.C) return;
-  double step = 0, xn = 0;
+  double step = 0, xn = 0, mcc = 0;
   if (c < d.C) {
-    double dl[6];
+    double dl[6], dyc[BD];
+#pragma unroll
     for (int k = 0; k < 6; ++k) {
       const int j = 6 * c + k;
       const double dyv = w.active[j] ? w.scale_c[j] * w.rhs[j] : 0.0;
       w.dy[j] = dyv;
+      dyc[k] = dyv;
       dl[k] = -dyv;
     }
     double qn[4];
-    quat_plus(pb.cam_q + 4 * c, dl, qn);
+    quat_plus_select(pb.cam_q + 4 * c, dl, qn);
     // |x| counts only blocks Ceres keeps in the reduced program (a constant pose is removed from it)
     const bool pose_var = !(pb.cam_const && (pb.cam_const[c] & 1u));
+#pragma unroll
     for (int k = 0; k < 4; ++k) { w.cand_q[4 * c + k] = qn[k]; const double df = qn[k] - pb.cam_q[4 * c + k]; step += df * df; if (pose_var) xn += pb.cam_q[4 * c + k] * pb.cam_q[4 * c + k]; }
+#pragma unroll
     for (int k = 0; k < 3; ++k) { const double tn = pb.cam_t[3 * c + k] + dl[3 + k]; w.cand_t[3 * c + k] = tn; step += dl[3 + k] * dl[3 + k]; if (pose_var) xn += pb.cam_t[3 * c + k] * pb.cam_t[3 * c + k]; }
+    if (cam_mcc) {
+#pragma unroll
+      for (int k = 0; k < KD; ++k) {
+        const int j = 6 * d.C + KD * (d.shared ? 0 : c) + k;
+        dyc[6 + k] = w.active[j] ? w.scale_c[j] * w.rhs[j] : 0.0;
+      }
+      const double* U = w.U + (size_t)c * BD * BD;
+      const double* g = w.g + (size_t)c * BD;
+      double lin = 0, quad = 0;
+#pragma unroll
+      for (int i = 0; i < BD; ++i) {
+        double ud = 0;
+#pragma unroll
+        for (int k = 0; k < BD; ++k) ud += U[i * BD + k] * dyc[k];
+        lin += dyc[i] * g[i];
+        quad += dyc[i] * ud;
+      }
+      mcc = lin - 0.5 * quad;
+    }
   }
   // intrinsics block a == c (per camera) or block 0 handled by the extra thread c == C (shared)
   const int a = d.shared ? ((c == d.C) ? 0 : -1) : ((c < d.C) ? c : -1);
   if (a >= 0) {
+    // (statically indexed throughout: an array indexed by a run-time slot is a stack object, and point_step_kernel, which
+    //  runs this body in its prologue, has no scratch)
     double in4[4];
+#pragma unroll
     for (int k = 0; k < 4; ++k) in4[k] = pb.intr[4 * a + k];
+#pragma unroll
     for (int k = 0; k < KD; ++k) {
       const int j = 6 * d.C + KD * a + k;
       const double dyv = w.active[j] ? w.scale_c[j] * w.rhs[j] : 0.0;
       w.dy[j] = dyv;
-      const int slot = (KD == 2) ? (k == 0 ? 0 : 3) : (d.only_k ? 3 : 0);
-      in4[slot] -= dyv;
+      const bool extra = (KD == 2) ? (k == 1) : (d.only_k != 0);    // the entry steps k (slot 3), else f (slot 0)
+      if (extra) in4[3] -= dyv; else in4[0] -= dyv;
       step += dyv * dyv;
     }
     const bool intr_var = KD > 0 && !(pb.intr_const && pb.intr_const[a]);
     const int np = (d.model == kSimpleRadial) ? 4 : 3;
+#pragma unroll
     for (int k = 0; k < 4; ++k) { w.cand_intr[4 * a + k] = in4[k]; if (intr_var && k < np) xn += pb.intr[4 * a + k] * pb.intr[4 * a + k]; }
   }
-  // (no camera-side share of the model cost change: point_step_kernel sums it observation by observation)
+  // (cam_mcc off: point_step_kernel<.., DIR = false> sums the cameras' share observation by observation)
   w.cam_part[3 * c] = step;
   w.cam_part[3 * c + 1] = xn;
-  w.cam_part[3 * c + 2] = 0.0;
+  w.cam_part[3 * c + 2] = mcc;
+}
+
+// (a launch of its own where point_step_kernel does not run the body in its prologue: a camera table over 64 KB, the
+//  separate glue launches)
+template <int KD>
+__global__ void cam_update_kernel(DevProblem pb, Ws w, int cam_mcc) {
+  if (w.ctl->done) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > pb.d.C) return;
+  cam_update_body<KD>(pb, w, c, cam_mcc != 0);
 }
 
 // back-substitution, model cost change and candidate point: LPP lanes per point (see point_pass_kernel).  The candidate's
 // cost is not evaluated here: cam_pass<CAND> behind this launch evaluates the candidate's residuals with their Jacobians, and
 // its cost decides the step.  (A second sweep here used to evaluate the same residuals for the cost alone, and after an
 // accepted step cam_pass<LIN> evaluated them once more; c3: this launch 0.101 -> 0.079 ms without that sweep.)
-template <int KD, bool LDSCAM, int LPP, bool LONGT = false>
-__global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem pb, Ws w) {
+//
+// DIR: the sweep in directional form.  What it needs of an observation is fy = F dy_c -- ONE directional derivative along the
+// camera's step -- and the adjoint product E^T fy = R^T JY^T fy, so neither the 2 x BD block F nor the 2 x 3 block E is built
+// (obs_step_R, camera_model.hpp).  dy is zero in every inactive column (cam_update_body; init_kernel derives `active` from
+// cam_const / intr_const exactly as eval_full masks F), so the constant-parameter masks of F drop out; a constant point
+// contributes nothing, as E = 0 did.  The cameras' share of the model cost change comes from cam_update_body, camera by
+// camera from U | g, so under the trivial loss the sweep needs no residual at all.  Robust loss (kernel-uniform branch):
+// the corrector C = sqrt(rho') (I - alpha r r^T) multiplies both Jacobians from the left, fy' = C fy and E'^T fy' = E^T C fy'.
+// DIR = false (vgg_ba_set_tile_rhs(| 8)) is the sweep over full Jacobians it replaced, for A/B runs in one library.
+//
+// fused (LDSCAM only): no cam_update launch in front.  Every workgroup fills its LDS table of dy from active / scale_c / rhs
+// -- the sweep reads NO w.dy from global memory, which another workgroup of this launch may not have written yet -- and the
+// LAST workgroup (one per 256 cameras) runs cam_update_body, a thread per camera (w.dy, the candidate cameras, cam_part: read
+// by later launches only).  The last ones because their wavefronts have the fewest points when P is no multiple of the
+// launch's stride.
+template <int KD, bool LDSCAM, int LPP, bool LONGT = false, bool DIR = true>
+__global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem pb, Ws w, int fused) {
   constexpr int BD = 6 + KD;
   __shared__ double red[4][3];
-  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy_pose[6C] flags[C]
+  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy[6C + KD NI = n_red], and DIR = false: flags[C] (bytes)
   if (w.ctl->done) return;
   const Dims& d = pb.d;
   constexpr int PPW = 64 / LPP;
@@ -2302,18 +2400,37 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
   const double* lq = cam_cache;                  // rotation matrices [9C]
   const double* lt = lq + 9 * d.C;
   const double* ldy = lt + 3 * d.C;
-  const double* lfl = ldy + 6 * d.C;
+  const double* ldi = ldy + 6 * d.C;              // the intrinsics entries of dy [KD NI]
+  // DIR = false: the cameras' constant-parameter flags [C] (DIR needs no masks).  Bytes: with doubles the table of 400 cameras
+  // with their own intrinsics would not fit into 64 KB
+  const uint8_t* lfl = reinterpret_cast<const uint8_t*>(ldi + KD * d.NI);
   if (LDSCAM) {
     double* cc = cam_cache;
     for (int i = threadIdx.x; i < d.C; i += 256) {
       quat_to_R(pb.cam_q + 4 * i, cc + 9 * i);
-      cc[18 * d.C + i] = pb.cam_const ? (double)pb.cam_const[i] : 0.0;
+      if (!DIR) reinterpret_cast<uint8_t*>(cc + 12 * d.C + d.n_red)[i] = pb.cam_const ? pb.cam_const[i] : (uint8_t)0;
     }
     for (int i = threadIdx.x; i < 3 * d.C; i += 256) cc[9 * d.C + i] = pb.cam_t[i];
-    for (int i = threadIdx.x; i < 6 * d.C; i += 256) cc[(ldy - cam_cache) + i] = w.dy[i];
+    // dy: the poses' entries first, then the intrinsics', as in w.dy
+    if (fused) {
+      // (the products cam_update_body stores in w.dy, made here from the same operands: the same bits; unrolled so that
+      //  the loads of four entries are in flight together -- 3200 entries at 400 cameras with their own intrinsics)
+#pragma unroll 4
+      for (int i = threadIdx.x; i < d.n_red; i += 256) cc[12 * d.C + i] = w.active[i] ? w.scale_c[i] * w.rhs[i] : 0.0;
+      // the last ceil((C + 1) / 256) workgroups take 256 cameras each (fewer workgroups than that: they take turns)
+      const int nbody = min((int)gridDim.x, (d.C + 256) / 256);
+      const int jb = (int)gridDim.x - 1 - (int)blockIdx.x;
+      if (jb < nbody) {
+        for (int c = jb * 256 + threadIdx.x; c <= d.C; c += 256 * nbody) cam_update_body<KD>(pb, w, c, DIR);
+        if (jb == 0 && threadIdx.x == 0) w.ctl->fused_step_prologues += 1;
+      }
+    } else {
+#pragma unroll 4
+      for (int i = threadIdx.x; i < d.n_red; i += 256) cc[12 * d.C + i] = w.dy[i];
+    }
     __syncthreads();
   }
-  (void)lfl;
+  (void)lfl; (void)ldi;
   // same software pipeline over the points of a wavefront as in point_pass_kernel
   int p = (blockIdx.x * 4 + wave) * PPW + sub;
   constexpr int NPF = LONGT ? 4 : 2;             // prefetched observations per lane (see point_pass_kernel)
@@ -2373,6 +2490,40 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
       const int c = f_pf.cam(pass, pb.obs_cam, o);
       const float2 uv = f_pf.uv(pass, pb.obs_uv, o);
       const int a = d.shared ? 0 : c;
+      if constexpr (DIR) {
+        double dyp[6], di[2] = {0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) dyp[k] = LDSCAM ? ldy[6 * c + k] : w.dy[6 * c + k];
+#pragma unroll
+        for (int k = 0; k < KD; ++k) di[k] = LDSCAM ? ldi[KD * a + k] : w.dy[6 * d.C + KD * a + k];
+        const double df = (KD == 2 || (KD == 1 && !d.only_k)) ? di[0] : 0.0;
+        const double dk = (KD == 2) ? di[1] : ((KD == 1 && d.only_k) ? di[0] : 0.0);
+        double Rg[9];
+        const double* Rc = lq + 9 * c;
+        if (!LDSCAM) { quat_to_R(pb.cam_q + 4 * c, Rg); Rc = Rg; }
+        const ObsStep s = obs_step_R(d.model, Rc, LDSCAM ? lt + 3 * c : pb.cam_t + 3 * c, pb.intr + 4 * a, X, dyp, df, dk,
+                                     (double)uv.x, (double)uv.y);
+        double y[2] = {s.fy[0], s.fy[1]};
+        if (d.loss != kLossTrivial) {
+          const double sq = s.r[0] * s.r[0] + s.r[1] * s.r[1];
+          double rho[3];
+          loss_eval(d.loss, d.loss_scale, sq, rho);
+          const Corrector cor(sq, rho);
+#pragma unroll
+          for (int rep = 0; rep < 2; ++rep) {        // fy' = C fy, then C fy' for the adjoint
+            const double rty = cor.alpha_sq_norm * (s.r[0] * y[0] + s.r[1] * y[1]);
+            y[0] = cor.sqrt_rho1 * (y[0] - s.r[0] * rty);
+            y[1] = cor.sqrt_rho1 * (y[1] - s.r[1] * rty);
+          }
+        }
+        double v3[3];
+        s.adjoint(y, v3);
+        if (!pt_c) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) t3[k] += Rc[k] * v3[0] + Rc[3 + k] * v3[1] + Rc[6 + k] * v3[2];
+        }
+        return;
+      }
       double r[2], F[2 * BD], E[6];
       if (LDSCAM)
         eval_full<KD>(d, lq + 9 * c, lt + 3 * c, pb.intr + 4 * a, X, uv, (unsigned)lfl[c],
@@ -2384,7 +2535,7 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
 #pragma unroll
       for (int k = 0; k < 6; ++k) { const double v = LDSCAM ? ldy[6 * c + k] : w.dy[6 * c + k]; fy0 += F[k] * v; fy1 += F[BD + k] * v; }
 #pragma unroll
-      for (int k = 0; k < KD; ++k) { const double v = w.dy[6 * d.C + KD * a + k]; fy0 += F[6 + k] * v; fy1 += F[BD + 6 + k] * v; }
+      for (int k = 0; k < KD; ++k) { const double v = LDSCAM ? ldi[KD * a + k] : w.dy[6 * d.C + KD * a + k]; fy0 += F[6 + k] * v; fy1 += F[BD + 6 + k] * v; }
       t3[0] += E[0] * fy0 + E[3] * fy1; t3[1] += E[1] * fy0 + E[4] * fy1; t3[2] += E[2] * fy0 + E[5] * fy1;
       s_mcc += fy0 * (r[0] - 0.5 * fy0) + fy1 * (r[1] - 0.5 * fy1);
     };
@@ -2919,23 +3070,33 @@ static int phase_step(const Launch& L) {
                                 L.chol_split_a, L.chol_split_b, L.chol_first_blk, true);
   }
   if (rc != VGG_OK) return rc;
-  cam_update_kernel<KD><<<div_up(d.C + 1, 64), 64, 0, L.st>>>(L.dp, L.w);
+  const bool dir = !g_tuning.legacy_step;
+  // the camera table of point_step in LDS: R, t per camera, dy, and a flag byte per camera for the sweep over full Jacobians
+  const size_t cam_lds = sizeof(double) * (12 * (size_t)d.C + (size_t)d.n_red) + (dir ? 0 : align_up((size_t)d.C, 8));
+  const bool lds_cam = cam_lds <= 64 * 1024;
+  // cam_update's body in point_step's prologue: with the LDS table only (without it the sweep reads w.dy from global memory)
+  const int fused = (lds_cam && !g_tuning.legacy_glue) ? 1 : 0;
+  if (!fused) cam_update_kernel<KD><<<div_up(d.C + 1, 64), 64, 0, L.st>>>(L.dp, L.w, dir ? 1 : 0);
   {
     ProfScope ps(kProfPointStep, L.st);
-    const size_t cam_lds = sizeof(double) * 19 * (size_t)d.C;
-    auto launch = [&](auto lpp) {
+    auto launch = [&](auto lpp, auto dirc) {
       constexpr int LPP = decltype(lpp)::value;
+      constexpr bool DIR = decltype(dirc)::value;
       const bool longt = long_tracks(LPP, L.d.P, L.d.O);
       if (longt && LPP <= 32) {
-        if (cam_lds <= 64 * 1024) point_step_kernel<KD, true, LPP, (LPP <= 32)><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w);
-        else point_step_kernel<KD, false, LPP, (LPP <= 32)><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
-      } else if (cam_lds <= 64 * 1024) point_step_kernel<KD, true, LPP><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w);
-      else point_step_kernel<KD, false, LPP><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w);
+        if (lds_cam) point_step_kernel<KD, true, LPP, (LPP <= 32), DIR><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w, fused);
+        else point_step_kernel<KD, false, LPP, (LPP <= 32), DIR><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w, 0);
+      } else if (lds_cam) point_step_kernel<KD, true, LPP, false, DIR><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w, fused);
+      else point_step_kernel<KD, false, LPP, false, DIR><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w, 0);
     };
-    if (L.lpp == 8) launch(std::integral_constant<int, 8>{});
-    else if (L.lpp == 16) launch(std::integral_constant<int, 16>{});
-    else if (L.lpp == 32) launch(std::integral_constant<int, 32>{});
-    else launch(std::integral_constant<int, 64>{});
+    auto launch_lpp = [&](auto dirc) {
+      if (L.lpp == 8) launch(std::integral_constant<int, 8>{}, dirc);
+      else if (L.lpp == 16) launch(std::integral_constant<int, 16>{}, dirc);
+      else if (L.lpp == 32) launch(std::integral_constant<int, 32>{}, dirc);
+      else launch(std::integral_constant<int, 64>{}, dirc);
+    };
+    if (dir) launch_lpp(std::true_type{});
+    else launch_lpp(std::false_type{});
   }
   {
     // the candidate's cost and, should the step be accepted, the next linearisation (bench.py's cam_pass<linearize> slot)
@@ -3085,15 +3246,18 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
   if (!(lanes_per_point == 0 || lanes_per_point == 8 || lanes_per_point == 16 || lanes_per_point == 32 || lanes_per_point == 64))
     return VGG_ERR_INVALID_ARGUMENT;
   vgg::g_tuning = vgg::Tuning{lanes_per_point, long_tracks < 0 ? -1 : (long_tracks ? 1 : 0), cam_workgroups > 0 ? cam_workgroups : 0,
-                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs, vgg::g_tuning.legacy_glue};
+                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs, vgg::g_tuning.legacy_glue,
+                              vgg::g_tuning.legacy_step};
   return VGG_OK;
 }
 
 int vgg_ba_set_tile_rhs(int enable) {
-  // bits 0..1: 0 / 1 / 2 as include/vggsfm_amd.h describes them; bit 2: keep the separate glue launches
-  const bool known = enable >= 0 && enable <= 7 && (enable & 3) <= 2;
+  // bits 0..1: 0 / 1 / 2 as include/vggsfm_amd.h describes them; bit 2: keep the separate glue launches; bit 3: keep the
+  // back-substitution sweep over full Jacobians
+  const bool known = enable >= 0 && enable <= 15 && (enable & 3) <= 2;
   vgg::g_tuning.tile_rhs = known ? (enable & 3) : 1;
   vgg::g_tuning.legacy_glue = (known && (enable & 4)) ? 1 : 0;
+  vgg::g_tuning.legacy_step = (known && (enable & 8)) ? 1 : 0;
   return VGG_OK;
 }
 

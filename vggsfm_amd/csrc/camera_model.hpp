@@ -49,6 +49,21 @@ __device__ __forceinline__ void quat_plus(const double* x, const double* d, doub
   out[2] = qw * x[2] + qx * x[1] - qy * x[0] + qz * x[3];
 }
 
+// quat_plus without the early return: the same expressions, the result chosen by selects.  (With the return `out` is written
+// on two paths and stays a stack object -- 32 bytes of scratch in every kernel that inlines quat_plus; for kernels that must
+// have none.  n == 0: sin(n) / n is NaN and is not selected.)
+__device__ __forceinline__ void quat_plus_select(const double* x, const double* d, double* out) {
+  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  const bool zero = n == 0.0;
+  const double s = sin(n) / n;
+  const double qx = s * d[0], qy = s * d[1], qz = s * d[2], qw = cos(n);
+  const double o3 = qw * x[3] - qx * x[0] - qy * x[1] - qz * x[2];
+  const double o0 = qw * x[0] + qx * x[3] + qy * x[2] - qz * x[1];
+  const double o1 = qw * x[1] - qx * x[2] + qy * x[3] + qz * x[0];
+  const double o2 = qw * x[2] + qx * x[1] - qy * x[0] + qz * x[3];
+  out[0] = zero ? x[0] : o0; out[1] = zero ? x[1] : o1; out[2] = zero ? x[2] : o2; out[3] = zero ? x[3] : o3;
+}
+
 // residual only
 __device__ __forceinline__ void obs_residual(int model, const double* q, const double* t, const double* intr,
                                              const double* X, double u_obs, double v_obs, double* r) {
@@ -145,6 +160,48 @@ __device__ __forceinline__ void obs_eval_R(int model, const double* R, const dou
   }
   Ji[0] = u * d; Ji[1] = f * r2 * u;
   Ji[2] = v * d; Ji[3] = f * r2 * v;
+}
+
+// One observation of the back-substitution sweep in DIRECTIONAL form: fy = F dy, the directional derivative of the residual
+// along the camera's step (dpose: rotation tangent (3), translation (3); df, dk: the steps of f and k, 0 where not refined),
+// and the adjoint product JY^T y in the CAMERA frame (the caller rotates it back: E^T y = R^T JY^T y) -- without the 2 x 6,
+// 2 x 2 and 2 x 3 Jacobians of obs_eval_R.  With a = R X and Jp of obs_eval_R (per row j of JY: J_delta = 2 (a x j), J_t = j):
+//   F_pose dpose = JY w,  w = 2 (d_omega x a) + dt;     JY = iz [xu xv -(xu u + xv v); xv yv -(xv u + yv v)].
+// r is the uncorrected residual (only a robust loss needs it; the compiler drops it otherwise).
+struct ObsStep {
+  double fy[2], r[2];
+  double iz, u, v, xu, xv, yv;
+  __device__ __forceinline__ void adjoint(const double* y, double* v3) const {
+    const double s0 = (xu * y[0] + xv * y[1]) * iz, s1 = (xv * y[0] + yv * y[1]) * iz;
+    v3[0] = s0; v3[1] = s1; v3[2] = -(u * s0 + v * s1);
+  }
+};
+__device__ __forceinline__ ObsStep obs_step_R(int model, const double* R, const double* t, const double* intr, const double* X,
+                                              const double* dpose, double df, double dk, double u_obs, double v_obs) {
+  ObsStep s;
+  double a[3];
+  a[0] = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
+  a[1] = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];
+  a[2] = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
+  const double Y0 = a[0] + t[0], Y1 = a[1] + t[1], Y2 = a[2] + t[2];
+  const double f = intr[0];
+  const double k = (model == kSimpleRadial) ? intr[3] : 0.0;
+  const double iz = 1.0 / Y2;
+  const double u = Y0 * iz, v = Y1 * iz;
+  const double r2 = u * u + v * v;
+  const double d = 1.0 + k * r2;
+  s.r[0] = f * (u * d) + intr[1] - u_obs;
+  s.r[1] = f * (v * d) + intr[2] - v_obs;
+  s.xu = f * (d + 2 * k * u * u); s.xv = f * (2 * k * u * v); s.yv = f * (d + 2 * k * v * v);
+  const double w0 = 2.0 * (dpose[1] * a[2] - dpose[2] * a[1]) + dpose[3];
+  const double w1 = 2.0 * (dpose[2] * a[0] - dpose[0] * a[2]) + dpose[4];
+  const double w2 = 2.0 * (dpose[0] * a[1] - dpose[1] * a[0]) + dpose[5];
+  const double p0 = (w0 - u * w2) * iz, p1 = (w1 - v * w2) * iz;
+  const double gi = d * df + (f * r2) * dk;        // Ji (df, dk)^T = (u, v) gi
+  s.fy[0] = s.xu * p0 + s.xv * p1 + u * gi;
+  s.fy[1] = s.xv * p0 + s.yv * p1 + v * gi;
+  s.iz = iz; s.u = u; s.v = v;
+  return s;
 }
 
 // Ceres LossFunction::Evaluate

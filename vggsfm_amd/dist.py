@@ -315,6 +315,7 @@ class ShardedBA:
                 self._split = True
 
     def begin(self):
+        BA.apply_launch_hooks(self.L)            # (measurement hooks behind VGGSFM_AMD_DEBUG_HOOKS, as BA.solve)
         _lib.check(self.L.vgg_ba_begin(*self._abi, self.nbytes, self.rank, self.world, _lib.stream_ptr()), "vgg_ba_begin")
 
     def _phase(self, i):
