@@ -305,7 +305,15 @@ int vgg_pose_refine(const double* points3D, const void* tracks, int tracks_are_f
  *   [num_frames / frames_per_sample_set][num_hypotheses][3] int32 indices into num_points (distinct, candidates),
  *   max_error_sq [num_frames] f64 (squared threshold on the normalised plane = (max_error / focal)^2).
  * Outputs per virtual frame: out_pose [12] row-major [R|t] (zeros if nothing found), out_num_inliers (0 if nothing
- * found), out_residual_sum, out_best (hypothesis * 4 + solution, -1 if none), out_inlier_mask [num_points]. */
+ * found), out_residual_sum, out_best (hypothesis * 4 + solution, -1 if none), out_inlier_mask [num_points].
+ * workspace: vgg_p3p_ransac_workspace_bytes(num_frames, num_hypotheses) bytes of device memory owned by the caller.
+ * Two of its blocks are readable after the call (once the stream has been synchronised); with FH = num_frames *
+ * num_hypotheses:
+ *   hypotheses  [num_frames][num_hypotheses][4][12] f64 at byte 0: the up to four poses of every sample, row-major
+ *               [R|t], zeros where the solution is not valid
+ *   validity    [num_frames][num_hypotheses][4] uint8 (0 / 1) at byte FH * 432, the last block (after the hypotheses,
+ *               FH * 4 f64 residual sums and FH * 4 int32 inlier counts, which are scratch)
+ * out_best indexes the hypotheses of its frame as a flat [4 * num_hypotheses][12] array. */
 size_t vgg_p3p_ransac_workspace_bytes(int num_frames, int num_hypotheses);
 int vgg_p3p_ransac(const double* points2D_normalized, const double* points3D, const uint8_t* candidate_mask,
                    const int32_t* samples, int num_frames, int frames_per_sample_set, int num_points, int num_hypotheses,

@@ -21,7 +21,9 @@ Only ``tests/`` may import this module.
 """
 import numpy as np
 
-NEWTON_ITERS = 80        # resolvent cubic: Newton from the Cauchy bound (monotone towards the largest real root)
+BISECT_ITERS = 60        # resolvent cubic: halvings of [0, Cauchy bound] (kBisectIters in csrc/p3p.hip)
+RESOLVENT_NEWTON = 4     # ... and guarded Newton steps inside the final bracket (kResolventNewton)
+POLISH_ITERS = 8         # Newton steps on the quartic per Ferrari root (kPolishIters): 1e-3 off ends at rounding level
 FOCAL_SAMPLES, FOCAL_MIN, FOCAL_MAX = 30, 0.2, 5.0      # COLMAP AbsolutePoseEstimationOptions defaults
 
 
@@ -33,24 +35,53 @@ def focal_length_factors(estimate_focal_length):
     return FOCAL_MIN + (FOCAL_MAX - FOCAL_MIN) * i * i
 
 
+def _ceil_exponent(x, n):
+    """ceil(e / n) of the binary exponent e of x (|x| < 2^e; -12000 for x == 0), as an integer array"""
+    e = np.where(x == 0.0, -12000, np.frexp(x)[1].astype(np.int64))
+    return -((-e) // n)
+
+
 def solve_quartic(k4, k3, k2, k1, k0):
     """Real roots of k4 v^4 + ... + k0 (arrays of equal shape).  Returns (roots (...,4), valid (...,4)).
-    Ferrari: depressed quartic y^4 + p y^2 + q y + r, largest real root m of the resolvent cubic
-    m^3 + p m^2 + (p^2/4 - r) m - q^2/8, two quadratics; two Newton steps on the original quartic per root."""
+    Ferrari on the quartic or, when |k0| > |k4|, on the reversed one (roots 1 / v): depressed quartic y^4 + p y^2 + q y + r, scaled by a power of two y = sigma z so that |p|, |q|, |r| < 1; a
+    positive root m of the resolvent cubic g(m) = m^3 + p m^2 + (p^2/4 - r) m - q^2/8; two quadratics; POLISH_ITERS Newton
+    steps on the original quartic per root.  Every real root m > 0 of the resolvent splits the quartic into two real
+    quadratics, and g(0) = -q^2/8 <= 0 < g(B) at the Cauchy bound B, so [0, B] holds one: it is found by bisection, which
+    cannot lose it (Newton from B can: it is monotone only when the rightmost root is real, and it circles for ever round
+    the real part of a complex pair to the right of the single real root).  After the scaling B < 2.25, so BISECT_ITERS
+    halvings leave an interval of 2e-18 and the Newton steps that follow -- each taken only if it stays inside the
+    bracket -- bring a small root to full relative precision."""
     with np.errstate(all="ignore"):
-        b, c, d, e = k3 / k4, k2 / k4, k1 / k4, k0 / k4
+        # solved in 1 / v when |k0| > |k4|: a leading coefficient of 1e-5 of the others sends one root to 1e5, and the shift
+        # by b / 4 then costs the other three ten digits; no root wanted here is 0
+        rev = np.abs(k0) > np.abs(k4)
+        a4, a3, a1, a0 = np.where(rev, k0, k4), np.where(rev, k1, k3), np.where(rev, k3, k1), np.where(rev, k4, k0)
+        b, c, d, e = a3 / a4, k2 / a4, a1 / a4, a0 / a4
         b2 = b * b
         p = c - 0.375 * b2
         q = d - 0.5 * b * c + 0.125 * b2 * b
         r = e - 0.25 * b * d + 0.0625 * b2 * c - (3.0 / 256.0) * b2 * b2
+        fin = np.isfinite(p) & np.isfinite(q) & np.isfinite(r)
+        ks = np.maximum(_ceil_exponent(p, 2), np.maximum(_ceil_exponent(q, 3), _ceil_exponent(r, 4)))
+        ks = np.where(fin, np.clip(ks, -300, 300), 0)
+        sigma, inv = np.ldexp(1.0, ks), np.ldexp(1.0, -ks)       # exact: the scaling changes no rounding
+        inv2 = inv * inv
+        p, q, r = p * inv2, q * inv2 * inv, r * inv2 * inv2
         c1 = 0.25 * p * p - r
         c0 = -0.125 * q * q
-        m = 1.0 + np.maximum(np.abs(p), np.maximum(np.abs(c1), np.abs(c0)))
-        for _ in range(NEWTON_ITERS):
+        lo = np.zeros_like(p)
+        hi = 1.0 + np.maximum(np.abs(p), np.maximum(np.abs(c1), np.abs(c0)))
+        for _ in range(BISECT_ITERS):
+            mid = 0.5 * (lo + hi)
+            pos = ((mid + p) * mid + c1) * mid + c0 > 0.0
+            hi = np.where(pos, mid, hi)
+            lo = np.where(pos, lo, mid)
+        m = 0.5 * (lo + hi)
+        for _ in range(RESOLVENT_NEWTON):
             g = ((m + p) * m + c1) * m + c0
             dg = (3.0 * m + 2.0 * p) * m + c1
-            step = np.where(dg != 0.0, g / dg, 0.0)
-            m = m - step
+            mn = m - g / dg
+            m = np.where((mn >= lo) & (mn <= hi), mn, m)
         scale = 1.0 + np.abs(p) + np.abs(m)
         roots = np.zeros(k4.shape + (4,))
         valid = np.zeros(k4.shape + (4,), bool)
@@ -67,7 +98,7 @@ def solve_quartic(k4, k3, k2, k1, k0):
             roots[..., 2 * j + 1] = 0.5 * (sg * s - sq)
             valid[..., 2 * j] = ok
             valid[..., 2 * j + 1] = ok
-        # biquadratic case: y^2 = (-p +- sqrt(p^2 - 4 r)) / 2
+        # biquadratic case: z^2 = (-p +- sqrt(p^2 - 4 r)) / 2
         dq = p * p - 4.0 * r
         dq = np.where((dq < 0.0) & (dq > -1e-10 * scale * scale), 0.0, dq)
         okq = dq >= 0.0
@@ -80,13 +111,14 @@ def solve_quartic(k4, k3, k2, k1, k0):
             roots[..., 2 * j + 1] = np.where(biq, -y, roots[..., 2 * j + 1])
             valid[..., 2 * j] = np.where(biq, oky, valid[..., 2 * j])
             valid[..., 2 * j + 1] = np.where(biq, oky, valid[..., 2 * j + 1])
-        v = roots - 0.25 * b[..., None]
+        v = roots * sigma[..., None] - 0.25 * b[..., None]
+        v = np.where(rev[..., None], 1.0 / v, v)
         K4, K3, K2, K1, K0 = (x[..., None] for x in (k4, k3, k2, k1, k0))
-        for _ in range(2):
+        for _ in range(POLISH_ITERS):
             f = (((K4 * v + K3) * v + K2) * v + K1) * v + K0
             df = ((4.0 * K4 * v + 3.0 * K3) * v + 2.0 * K2) * v + K1
             v = v - np.where(df != 0.0, f / df, 0.0)
-        lead_ok = np.abs(k4) > 1e-14 * (np.abs(k4) + np.abs(k3) + np.abs(k2) + np.abs(k1) + np.abs(k0))
+        lead_ok = np.abs(a4) > 1e-14 * (np.abs(k4) + np.abs(k3) + np.abs(k2) + np.abs(k1) + np.abs(k0))
         valid &= lead_ok[..., None] & np.isfinite(v)
     return v, valid
 
@@ -139,13 +171,16 @@ def p3p_solve(x, X):
         okq = np.abs(Qv) > 1e-12 * (np.abs(q1) + np.abs(q0))[:, None]
         u = -Pv / np.where(okq, Qv, 1.0)
         den = 1.0 + u * u - 2.0 * u * c12[:, None]
-        # (u, v) must satisfy both quadratics (drops spurious roots of the resultant / of a clamped discriminant)
+        # (u, v) must satisfy both quadratics (drops spurious roots of the resultant / of a clamped discriminant): the
+        # residuals against the sum of the magnitudes of their own terms -- A13 and A23 reach 1e5 when X1 and X2 nearly coincide
         C1v = (c11[:, None] - v) * v + c10[:, None]
         C2v = A23[:, None] - v * v
         B2v = b21[:, None] * v + b20[:, None]
         r1 = (A1[:, None] * u + B1[:, None]) * u + C1v
         r2 = (A2[:, None] * u + B2v) * u + C2v
-        okr = (np.abs(r1) + np.abs(r2)) <= 1e-7 * (1.0 + u * u + v * v)
+        s1 = (A1[:, None] * np.abs(u) + np.abs(B1)[:, None]) * np.abs(u) + ((np.abs(c11)[:, None] + np.abs(v)) * np.abs(v) + np.abs(c10)[:, None])
+        s2 = (np.abs(A2)[:, None] * np.abs(u) + np.abs(B2v)) * np.abs(u) + (A23[:, None] + v * v)
+        okr = (np.abs(r1) + np.abs(r2)) <= 1e-7 * (s1 + s2)
         ok = okv & okq & okr & (v > 0.0) & (u > 0.0) & (den > 0.0) & ok0[:, None]
         d1 = np.sqrt(a12[:, None] / np.where(ok, den, 1.0))
         d2, d3 = u * d1, v * d1

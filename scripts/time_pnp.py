@@ -6,6 +6,9 @@ profiles/pnp_times.json.  Two shapes, each a median of --reps windows between de
                points, 30 % outliers, max_rounds = 10, started from the true pose disturbed by a thousandth; with the
                histogram of the rounds' outcome (how many frames gained support)
   pose_score   vggp_pose_score of the same frames with L = 4 poses each
+  p3p_ransac   vgg_p3p_ransac at F = 20 * 30 = 600 virtual frames of P = 4096 points, 30 % outliers, H = 1024 samples each (the
+               default of RANSACOptions.num_hypotheses): the minimal solver of one thread per sample, the scoring of one
+               wavefront per sample, the selection
 Beside each time: the bytes the launch has to move, computed here from the shapes (the 2-D points of a problem are read
 in two sweeps, its mask in three; the shared 3-D points stay in cache), and what rate that makes of the 6.3 TB/s the
 MI355X streams at best -- a statement about the traffic, not about the arithmetic, which the 12 x 12 Jacobi of one
@@ -104,6 +107,17 @@ def main():
     r.update(F=F, P=P, L=L)
     res["pose_score"] = r
     print("pose_score", json.dumps(r), flush=True)
+    del many, start, out, xn
+    F, P, H = 20 * 30, 4096, 1024
+    X, xn, ps, bad = scene(F, P, 0.3, 2)
+    thr = torch.full((F,), (6e-3) ** 2, dtype=torch.float64, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(3)
+    samples = pose.draw_minimal_samples(torch.ones(F, P, dtype=torch.bool, device="cuda"), H, g)
+    _, num, _, _, _ = pose.p3p_ransac(xn, X, None, samples, thr)
+    r = windows(lambda: pose.p3p_ransac(xn, X, None, samples, thr), a.reps, a.inner)
+    r.update(F=F, P=P, H=H, inliers=float(num.double().mean()), true_inliers=float((~bad).sum(1).double().mean()))
+    res["p3p_ransac"] = r
+    print("p3p_ransac", json.dumps(r), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)

@@ -43,7 +43,12 @@ def test_p3p_exact_recovery_and_valid_rotations():
     gt = np.concatenate([Rs, ts[..., None]], -1)
     err = np.abs(poses - gt[:, None]).max((-1, -2))
     err[~ok] = np.inf
-    assert (err.min(1) < 1e-6).mean() > 0.99                       # the true pose is among the <= 4 solutions
+    # the true pose is among the <= 4 solutions.  Measured on the CPU over seeds 1..8 of this family: 0 to 2 of the 3000
+    # triplets miss 1e-6 (2 at this seed, errors up to 2.4e-5: nearly double roots, where float64 gives no more -- the
+    # solver loses no root: tests/test_p3p_cases.py); 6 misses leave room for that spread (a Poisson count of mean ~1).
+    # With Newton on the resolvent from the Cauchy bound the solver lost 0.35 % of such triplets outright.
+    assert ok.any(1).all()
+    assert (err.min(1) < 1e-6).mean() >= 1.0 - 6.0 / H
     R = poses[ok][:, :, :3]
     np.testing.assert_allclose(R @ np.swapaxes(R, -1, -2), np.broadcast_to(np.eye(3), R.shape), atol=1e-9)
     np.testing.assert_allclose(np.linalg.det(R), 1.0, atol=1e-9)

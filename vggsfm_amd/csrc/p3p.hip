@@ -26,23 +26,56 @@
 
 namespace vgg {
 
-constexpr int kNewtonIters = 80;   // NEWTON_ITERS in oracle/p3p.py
+constexpr int kBisectIters = 60;      // BISECT_ITERS in oracle/p3p.py
+constexpr int kResolventNewton = 4;   // RESOLVENT_NEWTON
+constexpr int kPolishIters = 8;       // POLISH_ITERS
 
-// Real roots of k4 v^4 + k3 v^3 + k2 v^2 + k1 v + k0 (Ferrari; oracle/p3p.py solve_quartic).
+// ceil(e / n) of the binary exponent e of x (|x| < 2^e; -12000 for x == 0)
+__device__ inline int ceil_exponent(double x, int n) {
+  int e;
+  frexp(x, &e);
+  if (x == 0.0) e = -12000;
+  return e >= 0 ? (e + n - 1) / n : -((-e) / n);
+}
+
+// Real roots of k4 v^4 + k3 v^3 + k2 v^2 + k1 v + k0 (Ferrari; oracle/p3p.py solve_quartic).  The depressed quartic is
+// scaled by a power of two (exact) so that |p|, |q|, |r| < 1.  Every real root m > 0 of the resolvent cubic g splits the
+// quartic into two real quadratics, and g(0) = -q^2/8 <= 0 < g(B) at the Cauchy bound B < 2.25: bisection on [0, B]
+// cannot lose that root (Newton from B can: it is monotone only when the rightmost root is real), the guarded Newton
+// steps afterwards give a small root its full relative precision.
 __device__ inline void solve_quartic(double k4, double k3, double k2, double k1, double k0, double v[4], bool ok[4]) {
-  const double b = k3 / k4, c = k2 / k4, d = k1 / k4, e = k0 / k4;
+  // solved in 1 / v when |k0| > |k4|: a leading coefficient of 1e-5 of the others sends one root to 1e5, and the shift by
+  // b / 4 then costs the other three ten digits; no root wanted here is 0
+  const bool rev = fabs(k0) > fabs(k4);
+  const double a4 = rev ? k0 : k4, a3 = rev ? k1 : k3, a1 = rev ? k3 : k1, a0 = rev ? k4 : k0;
+  const double b = a3 / a4, c = k2 / a4, d = a1 / a4, e = a0 / a4;
   const double b2 = b * b;
-  const double p = c - 0.375 * b2;
-  const double q = d - 0.5 * b * c + 0.125 * b2 * b;
-  const double r = e - 0.25 * b * d + 0.0625 * b2 * c - (3.0 / 256.0) * b2 * b2;
+  double p = c - 0.375 * b2;
+  double q = d - 0.5 * b * c + 0.125 * b2 * b;
+  double r = e - 0.25 * b * d + 0.0625 * b2 * c - (3.0 / 256.0) * b2 * b2;
+  int ks = 0;
+  if (isfinite(p) && isfinite(q) && isfinite(r)) {
+    ks = max(ceil_exponent(p, 2), max(ceil_exponent(q, 3), ceil_exponent(r, 4)));
+    ks = min(max(ks, -300), 300);
+  }
+  const double sigma = ldexp(1.0, ks), inv = ldexp(1.0, -ks);
+  const double inv2 = inv * inv;
+  p = p * inv2; q = q * inv2 * inv; r = r * inv2 * inv2;
   const double c1 = 0.25 * p * p - r;
   const double c0 = -0.125 * q * q;
-  double m = 1.0 + fmax(fabs(p), fmax(fabs(c1), fabs(c0)));
-  for (int it = 0; it < kNewtonIters; ++it) {
+  double lo = 0.0, hi = 1.0 + fmax(fabs(p), fmax(fabs(c1), fabs(c0)));
+  for (int it = 0; it < kBisectIters; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    const bool pos = ((mid + p) * mid + c1) * mid + c0 > 0.0;
+    hi = pos ? mid : hi;
+    lo = pos ? lo : mid;
+  }
+  double m = 0.5 * (lo + hi);
+  for (int it = 0; it < kResolventNewton; ++it) {
     const double g = ((m + p) * m + c1) * m + c0;
     const double dg = (3.0 * m + 2.0 * p) * m + c1;
-    const double step = (dg != 0.0) ? g / dg : 0.0;
-    m = m - step;
+    const double mn = m - g / dg;
+    m = (mn >= lo && mn <= hi) ? mn : m;
   }
   const double scale = 1.0 + fabs(p) + fabs(m);
   const bool biq = !(m > 1e-14 * scale);
@@ -76,12 +109,12 @@ __device__ inline void solve_quartic(double k4, double k3, double k2, double k1,
       ok[2 * j] = oky; ok[2 * j + 1] = oky;
     }
   }
-  const bool lead_ok = fabs(k4) > 1e-14 * (fabs(k4) + fabs(k3) + fabs(k2) + fabs(k1) + fabs(k0));
+  const bool lead_ok = fabs(a4) > 1e-14 * (fabs(k4) + fabs(k3) + fabs(k2) + fabs(k1) + fabs(k0));
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    double x = roots[j] - 0.25 * b;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
+    double x = roots[j] * sigma - 0.25 * b;
+    x = rev ? 1.0 / x : x;
+    for (int it = 0; it < kPolishIters; ++it) {
       const double f = (((k4 * x + k3) * x + k2) * x + k1) * x + k0;
       const double df = ((4.0 * k4 * x + 3.0 * k3) * x + 2.0 * k2) * x + k1;
       x = x - ((df != 0.0) ? f / df : 0.0);
@@ -162,13 +195,16 @@ __global__ __launch_bounds__(128) void p3p_hypotheses_kernel(const double* __res
     const bool okq = fabs(Qv) > 1e-12 * (fabs(q1) + fabs(q0));
     const double u = -Pv / (okq ? Qv : 1.0);
     const double den = 1.0 + u * u - 2.0 * u * c12;
-    // (u, v) must satisfy both quadratics (drops spurious roots of the resultant / of a clamped discriminant)
+    // (u, v) must satisfy both quadratics (drops spurious roots of the resultant / of a clamped discriminant): the
+    // residuals against the sum of the magnitudes of their own terms -- A13, A23 reach 1e5 when X1 and X2 nearly coincide
     const double C1v = (c11 - vs) * vs + c10;
     const double C2v = A23 - vs * vs;
     const double B2v = b21 * vs + b20;
     const double r1 = (A1 * u + B1) * u + C1v;
     const double r2 = (A2 * u + B2v) * u + C2v;
-    const bool okr = (fabs(r1) + fabs(r2)) <= 1e-7 * (1.0 + u * u + vs * vs);
+    const double s1 = (A1 * fabs(u) + fabs(B1)) * fabs(u) + ((fabs(c11) + fabs(vs)) * fabs(vs) + fabs(c10));
+    const double s2 = (fabs(A2) * fabs(u) + fabs(B2v)) * fabs(u) + (A23 + vs * vs);
+    const bool okr = (fabs(r1) + fabs(r2)) <= 1e-7 * (s1 + s2);
     bool ok = okv[s] && okq && okr && vs > 0.0 && u > 0.0 && den > 0.0 && ok0;
     const double dd1 = sqrt(a12 / (ok ? den : 1.0));
     const double dd2 = u * dd1, dd3 = vs * dd1;
