@@ -262,7 +262,9 @@ int vgg_ba_solve(const vgg_ba_problem* problem, const vgg_ba_options* options, v
  *                      B's), buffer 6 = [A: W ca | B: W (cb + 1)] (all-gather outputs); buffers 4 and 6 are carved with the
  *                      padding both forms need up to W = 1024 (count(6) = count(4) + 3072)
  * vgg_ba_reduce_buffer returns the device address / element count (doubles) of each reduce buffer (which = 7: buffer 4's address
- * and the element count of part A). */
+ * and the element count of part A; which = 8: no reduce buffer but the solver's own Jacobi scales of the n reduced columns,
+ * 1 / (1 + sqrt(colsq)), or 1 without jacobi_scaling -- valid once phase 1 has run; include/vggsfm_amd_covariance.h undoes the
+ * scaling of buffer 1 with them). */
 int vgg_ba_begin(const vgg_ba_problem* problem, const vgg_ba_options* options, void* workspace, size_t workspace_bytes,
                  int rank, int world_size, void* stream);
 int vgg_ba_phase(const vgg_ba_problem* problem, const vgg_ba_options* options, void* workspace, int phase,

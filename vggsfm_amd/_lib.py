@@ -10,7 +10,7 @@ header and one row in that table (tests/test_host_logic.py compares the two, typ
 ``SIGNATURES`` are a closed set; the multi-view entries (include/vggsfm_amd_multiview.h, prefix ``vggx_``) have the table
 ``SIGNATURES_MULTIVIEW``, applied next to the first, and the essential-matrix entries (include/vggsfm_amd_essential.h, prefix
 ``vgge_emat_``) the table ``SIGNATURES_ESSENTIAL``, and the EPnP entries (include/vggsfm_amd_pnp.h, prefix ``vggp_``) the table
-``SIGNATURES_PNP``.
+``SIGNATURES_PNP``, and the covariance entries (include/vggsfm_amd_covariance.h, prefix ``vggc_``) the table ``SIGNATURES_COV``.
 """
 import ctypes
 import operator
@@ -186,6 +186,17 @@ SIGNATURES_PNP = {
 }
 EXPORTED_PNP = list(SIGNATURES_PNP)
 
+# The fifth table: the vggc_* entries of include/vggsfm_amd_covariance.h (csrc/covariance.hip, same library), in that header's
+# order.  tests/test_covariance_reference.py compares the two.
+SIGNATURES_COV = {
+    "vggc_spd_inverse_workspace_bytes": (_SIZE, [_I]),
+    "vggc_spd_inverse": (_INT, [_P, _I, _P, _P, _P]),
+    "vggc_ba_covariance_workspace_bytes": (_SIZE, [_P, _P, _I]),
+    "vggc_ba_covariance": (_INT, [_P, _P, _P, _Z, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+EXPORTED_COV = list(SIGNATURES_COV)
+COV_CAMERAS, COV_POINTS = 1, 2      # VGGC_COV_* of the header
+
 _lib = None
 
 
@@ -213,7 +224,7 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL, SIGNATURES_PNP):
+    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL, SIGNATURES_PNP, SIGNATURES_COV):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -942,6 +942,118 @@ def solve(problem: DeviceProblem, options: Optional[BundleAdjustmentOptions] = N
     return out, workspace
 
 
+# ------------------------------------------------------------------ covariance (include/vggsfm_amd_covariance.h)
+POSE_COMPONENTS = ("rx", "ry", "rz", "tx", "ty", "tz")     # rotation in the solver's tangent (HALF the rotation vector), translation
+
+
+@dataclass
+class BACovariance:
+    """(J^T J)^-1 at a problem's state, in the solver's tangent (rotation block in half-angle units: the covariance of the
+    rotation vector is 4 x that block, its cross terms 2 x), unit weights -- multiply by `variance_factor` for the a-posteriori
+    covariance.  Constant and unobserved parameters have zero blocks."""
+    pose: Optional[torch.Tensor]              # (S,6,6), the caller's frame order
+    intrinsics: Optional[torch.Tensor]        # (S or 1,kd,kd): the refined ones of (f, k); per camera in the caller's frame order
+    pose_intrinsics: Optional[torch.Tensor]   # (S,6,kd): a frame's pose against its own (or the shared) intrinsics
+    points: Optional[torch.Tensor]            # (P,3,3), the problem's point order
+    reduced: Optional[torch.Tensor]           # (n,n): all camera and intrinsics columns, in the PROBLEM's column order
+    columns: list                             # row i of `reduced` is (kind, index, component): ("pose", frame, "rx".."tz") or
+                                              # ("intrinsics", frame -- 0 for a shared camera --, "f" | "k")
+    num_active: int                           # active columns: cameras, intrinsics and points
+    variance_factor: float                    # 2 cost / (2 observations - active columns); reported, not multiplied in
+    cost: float
+
+
+def covariance_columns(problem: DeviceProblem):
+    """What each row of the reduced covariance is, with `cam_perm` undone: see BACovariance.columns."""
+    C, NI = problem.cam_t.shape[0], problem.intr.shape[0]
+    names = [nm for nm, on in (("f", problem.refine_focal), ("k", problem.refine_extra and problem.camera_model == 1)) if on]
+    frame = list(range(C)) if problem.cam_perm is None else [int(f) for f in problem.cam_perm.tolist()]
+    cols = [("pose", frame[c], comp) for c in range(C) for comp in POSE_COMPONENTS]
+    cols += [("intrinsics", 0 if NI == 1 else frame[a], nm) for a in range(NI) for nm in names]
+    return cols
+
+
+def active_columns(problem: DeviceProblem):
+    """(n,) bool on the problem's device: which columns of the reduced system take part -- a camera with observations whose
+    pose (or translation component) is not constant, an intrinsics block that is not constant and, per camera, observed: the
+    rule of the solver's init_kernel for one rank, which vggc_ba_covariance applies too."""
+    C, NI = problem.cam_t.shape[0], problem.intr.shape[0]
+    kd = int(bool(problem.refine_focal)) + int(bool(problem.refine_extra) and problem.camera_model == 1)
+    observed = problem.col_ptr[1:] > problem.col_ptr[:-1]
+    flags = problem.cam_const.long() if problem.cam_const is not None else torch.zeros_like(problem.col_ptr[1:], dtype=torch.long)
+    pose = (observed & ((flags & 1) == 0))[:, None].repeat(1, 6)
+    for k in range(3):
+        pose[:, 3 + k] &= (flags & (2 << k)) == 0
+    intr = torch.ones(NI, dtype=torch.bool, device=pose.device)
+    if problem.intr_const is not None:
+        intr &= problem.intr_const == 0
+    if NI > 1:
+        intr &= observed
+    return torch.cat([pose.reshape(-1), intr[:, None].repeat(1, kd).reshape(-1)])
+
+
+def to_frame_order(problem: DeviceProblem, per_camera):
+    """A per-camera tensor of the problem (first axis: its cameras) in the order of the caller's frames."""
+    if per_camera is None or problem.cam_perm is None:
+        return per_camera
+    inv = torch.empty_like(problem.cam_perm)
+    inv[problem.cam_perm] = torch.arange(problem.cam_perm.shape[0], device=problem.cam_perm.device)
+    return per_camera[inv.to(per_camera.device)]
+
+
+def estimate_covariance(problem: DeviceProblem, options: Optional[BundleAdjustmentOptions] = None, *, poses=True,
+                        intrinsics=True, points=False, reduced=False):
+    """Covariance of the problem's CURRENT state (vggc_ba_covariance): the state is not written, and a solve afterwards is what
+    it would have been.  Single GPU.  Host syncs: the one of vgg_ba_begin and one at the end (the failure flag and the cost).
+    Raises RuntimeError when the reduced system or a point block is not positive definite."""
+    L = _lib.lib()
+    options = options or BundleAdjustmentOptions()
+    problem.refine_focal = options.refine_focal_length
+    problem.refine_extra = options.refine_extra_params
+    problem.loss = LOSS_ID[options.loss_function_type]
+    problem.loss_scale = options.loss_function_scale
+    cp = problem.c_struct()
+    co = _c_options(options, overlap=False)
+    dev = problem.pts.device
+    C, NI, P = problem.cam_t.shape[0], problem.intr.shape[0], problem.pts.shape[0]
+    kd = int(bool(problem.refine_focal)) + int(bool(problem.refine_extra) and problem.camera_model == 1)
+    n = 6 * C + kd * NI
+    flags = _lib.COV_CAMERAS | (_lib.COV_POINTS if points else 0)
+    nbytes = L.vggc_ba_covariance_workspace_bytes(ctypes.byref(cp), ctypes.byref(co), flags)
+    if nbytes == 0:
+        raise RuntimeError("vggc_ba_covariance_workspace_bytes: unsupported problem")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    pose = new(C, 6, 6) if poses else None
+    intr = new(NI, kd, kd) if (kd and intrinsics) else None
+    pose_intr = new(C, 6, kd) if (kd and intrinsics) else None
+    red = new(n, n) if reduced else None
+    pts = new(P, 3, 3) if points else None
+    fail = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(L.vggc_ba_covariance(ctypes.byref(cp), ctypes.byref(co), ws, nbytes, flags, red, pose, intr, pose_intr, pts, fail,
+                                    _lib.stream_ptr()), "vggc_ba_covariance")
+    # the solver's workspace is the head of `ws`: reduce buffer 0 ends with the per-camera costs at this state
+    address, count = _lib.reduce_buffer(ctypes.byref(cp), ctypes.byref(co), ws, 0)
+    off = address - ws.data_ptr()
+    cost = 0.5 * ws[off:off + 8 * count].view(torch.float64)[count - C:].sum()
+    observed = problem.row_ptr[1:] > problem.row_ptr[:-1]
+    if problem.pt_const is not None:
+        observed = observed & (problem.pt_const == 0)
+    active = active_columns(problem).sum() + 3 * observed.sum()
+    vals = torch.stack([fail[0].double(), cost, active.double()]).tolist()         # (one copy, one synchronisation)
+    failed, cost, active = int(vals[0]), float(vals[1]), int(vals[2])
+    if failed:
+        raise RuntimeError("vggc_ba_covariance: the normal equations are not positive definite at this state -- the likely cause "
+                           "is a gauge that is not fixed (no constant pose, or no constant second-camera position component), "
+                           "or a parameter that no observation constrains")
+    dof = 2 * problem.num_obs - active
+    return BACovariance(pose=to_frame_order(problem, pose),
+                        intrinsics=to_frame_order(problem, intr) if NI > 1 else intr,
+                        pose_intrinsics=to_frame_order(problem, pose_intr), points=pts, reduced=red,
+                        columns=covariance_columns(problem), num_active=active,
+                        variance_factor=(2.0 * cost / dof) if dof > 0 else float("nan"), cost=cost)
+
+
 def normalization_transform(extrinsics, extent=5.0, p0=0.1, p1=0.9):
     """The similarity of Reconstruction.normalize(extent, p0, p1, True): (scale (), mean (3,), normalised extrinsics) --
     X -> scale (X - mean); None when there are fewer than two cameras."""
@@ -974,21 +1086,10 @@ def normalize_reconstruction(extrinsics, points3D, alive=None, extent=5.0, p0=0.
     return ext, pts
 
 
-def bundle_adjustment(points3d, extrinsics, intrinsics, tracks, masks, image_size=None, extra_params=None,
-                      shared_camera=False, camera_type="SIMPLE_PINHOLE", options=None, normalize=False,
-                      constant_points=None, constant_pose_frames=None, filter_negative_depth=True):
-    """Tensor-in / tensor-out equivalent of the reference's three-call round trip
-    (batch_matrix_to_pycolmap -> pycolmap.bundle_adjustment -> pycolmap_to_batch_matrix).
-    Returns (points3D_opt (P',3), extrinsics (S,3,4), intrinsics (S,3,3), extra_params (S,1)|None, summary);
-    P' = number of tracks with >= 2 masked observations, rows of deleted points are zero.
-
-    The two optional arguments express a ``pycolmap.BundleAdjustmentConfig`` (video_runner.py:813-829):
-    `constant_points` (P,) bool over the INPUT tracks = ``add_constant_point``; `constant_pose_frames` = the frames
-    of ``set_constant_cam_pose`` -- when given it REPLACES the default gauge of ``pycolmap.bundle_adjustment``
-    (frame 0 pose + frame 1 t_x constant).  `filter_negative_depth=False` for the BundleAdjuster-level entry
-    (``solve_bundle_adjustment``), which does not run the ObservationManager filter."""
-    _lib.require_gpu(points3d, extrinsics, intrinsics, tracks, masks)
-    options = options or BundleAdjustmentOptions()
+def _compile_call(points3d, extrinsics, intrinsics, tracks, masks, extra_params, shared_camera, camera_type, options,
+                  constant_points, constant_pose_frames, filter_negative_depth):
+    """The DeviceProblem of one ``bundle_adjustment`` call, gauge and constant blocks in place ->
+    (problem, valid_idx, deleted, inverse camera permutation | None, sort_points)."""
     sort_points = _hook("VGGSFM_SORT_POINTS", "1" if SORT_POINTS else "0") != "0"
     prob, valid_idx, deleted = compile_problem(points3d, extrinsics, intrinsics, tracks, masks, extra_params,
                                                shared_camera, camera_type, filter_negative_depth=filter_negative_depth,
@@ -1005,7 +1106,50 @@ def bundle_adjustment(points3d, extrinsics, intrinsics, tracks, masks, image_siz
         prob.cam_const[cf if inv_perm is None else inv_perm[cf]] = 1
     if constant_points is not None:
         prob.pt_const = constant_points.to(device=prob.pts.device)[valid_idx].to(torch.uint8).contiguous()
+    return prob, valid_idx, deleted, inv_perm, sort_points
+
+
+def covariance_of_call(points3d, extrinsics, intrinsics, tracks, masks, extra_params=None, shared_camera=False,
+                       camera_type="SIMPLE_PINHOLE", options=None, constant_points=None, constant_pose_frames=None,
+                       filter_negative_depth=True):
+    """``estimate_covariance`` (poses, intrinsics, points) of the problem ``bundle_adjustment`` would solve for the same
+    arguments, at the state given -- nothing is solved.  -> (BACovariance with `points` in the order of the valid tracks,
+    ascending, as points3D_opt; valid_idx (P',); deleted (P',))."""
+    _lib.require_gpu(points3d, extrinsics, intrinsics, tracks, masks)
+    options = options or BundleAdjustmentOptions()
+    prob, valid_idx, deleted, _, sort_points = _compile_call(points3d, extrinsics, intrinsics, tracks, masks, extra_params,
+                                                             shared_camera, camera_type, options, constant_points,
+                                                             constant_pose_frames, filter_negative_depth)
+    cov = estimate_covariance(prob, options, points=True)
+    if sort_points:
+        back = torch.argsort(valid_idx)
+        cov.points, deleted, valid_idx = cov.points[back], deleted[back], valid_idx[back]
+    return cov, valid_idx, deleted
+
+
+def bundle_adjustment(points3d, extrinsics, intrinsics, tracks, masks, image_size=None, extra_params=None,
+                      shared_camera=False, camera_type="SIMPLE_PINHOLE", options=None, normalize=False,
+                      constant_points=None, constant_pose_frames=None, filter_negative_depth=True, return_covariance=False):
+    """Tensor-in / tensor-out equivalent of the reference's three-call round trip
+    (batch_matrix_to_pycolmap -> pycolmap.bundle_adjustment -> pycolmap_to_batch_matrix).
+    Returns (points3D_opt (P',3), extrinsics (S,3,4), intrinsics (S,3,3), extra_params (S,1)|None, summary);
+    P' = number of tracks with >= 2 masked observations, rows of deleted points are zero.
+
+    The two optional arguments express a ``pycolmap.BundleAdjustmentConfig`` (video_runner.py:813-829):
+    `constant_points` (P,) bool over the INPUT tracks = ``add_constant_point``; `constant_pose_frames` = the frames
+    of ``set_constant_cam_pose`` -- when given it REPLACES the default gauge of ``pycolmap.bundle_adjustment``
+    (frame 0 pose + frame 1 t_x constant).  `filter_negative_depth=False` for the BundleAdjuster-level entry
+    (``solve_bundle_adjustment``), which does not run the ObservationManager filter.
+    `return_covariance`: summary["covariance"] = ``estimate_covariance`` (poses, intrinsics, points) at the solution, its
+    points indexed like the returned points3D_opt with zero blocks for deleted points; taken before `normalize` rescales."""
+    _lib.require_gpu(points3d, extrinsics, intrinsics, tracks, masks)
+    options = options or BundleAdjustmentOptions()
+    prob, valid_idx, deleted, inv_perm, sort_points = _compile_call(points3d, extrinsics, intrinsics, tracks, masks, extra_params,
+                                                                    shared_camera, camera_type, options, constant_points,
+                                                                    constant_pose_frames, filter_negative_depth)
+    S = extrinsics.shape[0]
     summary, _ = solve(prob, options)
+    cov = estimate_covariance(prob, options, points=True) if return_covariance else None
     ext = torch.cat([quat_to_rotmat(prob.cam_q), prob.cam_t[:, :, None]], -1)
     if inv_perm is not None:
         ext = ext[inv_perm]                           # back to the order of the input frames
@@ -1014,6 +1158,8 @@ def bundle_adjustment(points3d, extrinsics, intrinsics, tracks, masks, image_siz
     if sort_points:                                   # back to track order (the contract: rows of the valid tracks, ascending)
         back = torch.argsort(valid_idx)
         pts, deleted, valid_idx = pts[back], deleted[back], valid_idx[back]
+        if cov is not None:
+            cov.points = cov.points[back]
     if normalize:
         ext, pts = normalize_reconstruction(ext, pts, ~deleted)
     idx = torch.zeros(S, dtype=torch.long, device=pts.device) if shared_camera else \
@@ -1026,4 +1172,6 @@ def bundle_adjustment(points3d, extrinsics, intrinsics, tracks, masks, image_siz
     extra = prob.intr[idx, 3][:, None].clone() if camera_type == "SIMPLE_RADIAL" else None
     summary["valid_idx"] = valid_idx
     summary["deleted"] = deleted
+    if cov is not None:
+        summary["covariance"] = cov
     return pts, ext, K, extra, summary

@@ -3358,6 +3358,7 @@ int vgg_ba_reduce_buffer(const vgg_ba_problem* problem, const vgg_ba_options* op
     case 5: *device_ptr = w.pk_mine; *count = w.packed_count + 2; break;
     case 6: *device_ptr = w.pk_gathered; *count = w.packed_count + 3 * kPackPad; break;
     case 7: *device_ptr = w.packed; *count = split_count_a(d); break;      // (count = elements of part A of the split exchange)
+    case 8: *device_ptr = w.scale_c; *count = (size_t)d.n_red; break;      // (no reduce buffer: the Jacobi scales of the reduced columns)
     default: return VGG_ERR_INVALID_ARGUMENT;
   }
   return VGG_OK;

@@ -1043,6 +1043,33 @@ def bundle_adjustment(reconstruction, options=None):
     return _solve(reconstruction, options, None)
 
 
+def _config_constant_points(rec, cfg):
+    """The point3D ids a BundleAdjuster with config `cfg` holds constant on `rec` (BundleAdjuster._run, estimate_ba_covariance)."""
+    if cfg.constant_cam_positions:
+        raise NotImplementedError("BundleAdjustmentConfig.set_constant_cam_positions is not used by the reference")
+    # COLMAP BundleAdjuster::SetUp: a point whose track has observations in images OUTSIDE the config is held constant
+    # (its track length exceeds its observations inside the problem) unless it was named with add_variable_point.  The
+    # reference's call sites put every registered image into the config (video_runner.py:817-829), where this selects
+    # nothing.  COLMAP's tracks only hold REGISTERED images (DeRegisterImage deletes the observations): 2D points linked
+    # in an image that is not registered do not count.  A variable point with observations outside the config would need
+    # those images in the problem with constant poses (COLMAP adds them); the reference never builds such a config, so
+    # that case raises instead of silently losing the observations (ADVICE r3).
+    partly_outside = set()
+    if not set(rec.reg_image_ids()) <= set(cfg.image_ids):    # (every reference call site: the config holds them all)
+        ptr, timg, _ = rec._track_csr()
+        registered = np.isin(timg, np.asarray(rec.reg_image_ids(), np.int64))
+        inside = np.isin(timg, np.asarray(cfg.image_ids, np.int64))
+        pid_of_obs = np.repeat(np.arange(1, len(ptr)), np.diff(ptr))
+        partly_outside = {int(p) for p in np.unique(pid_of_obs[registered & ~inside])}
+    lost = partly_outside & set(cfg.variable_point3D_ids)
+    if lost:
+        raise NotImplementedError(f"BundleAdjustmentConfig: {len(lost)} variable point(s) (e.g. id {min(lost)}) are observed in "
+                                  "registered images outside the config; COLMAP would add those observations with constant "
+                                  "poses -- add the images to the config with set_constant_cam_pose")
+    constant = set(cfg.constant_point3D_ids) | partly_outside
+    return constant
+
+
 class _Problem:
     """What ``BundleAdjuster.problem`` hands to ``pyceres.solve``."""
 
@@ -1077,34 +1104,50 @@ class BundleAdjuster:
         opts = copy.copy(self.options)
         opts.solver_options = solver_options
         cfg = self.config
-        if cfg.constant_cam_positions:
-            raise NotImplementedError("BundleAdjustmentConfig.set_constant_cam_positions is not used by the reference")
-        # COLMAP BundleAdjuster::SetUp: a point whose track has observations in images OUTSIDE the config is held constant
-        # (its track length exceeds its observations inside the problem) unless it was named with add_variable_point.  The
-        # reference's call sites put every registered image into the config (video_runner.py:817-829), where this selects
-        # nothing.  COLMAP's tracks only hold REGISTERED images (DeRegisterImage deletes the observations): 2D points linked
-        # in an image that is not registered do not count.  A variable point with observations outside the config would need
-        # those images in the problem with constant poses (COLMAP adds them); the reference never builds such a config, so
-        # that case raises instead of silently losing the observations.
-        rec = self.reconstruction
-        partly_outside = set()
-        if not set(rec.reg_image_ids()) <= set(cfg.image_ids):    # (every reference call site: the config holds them all)
-            ptr, timg, _ = rec._track_csr()
-            registered = np.isin(timg, np.asarray(rec.reg_image_ids(), np.int64))
-            inside = np.isin(timg, np.asarray(cfg.image_ids, np.int64))
-            pid_of_obs = np.repeat(np.arange(1, len(ptr)), np.diff(ptr))
-            partly_outside = {int(p) for p in np.unique(pid_of_obs[registered & ~inside])}
-        lost = partly_outside & set(cfg.variable_point3D_ids)
-        if lost:
-            raise NotImplementedError(f"BundleAdjustmentConfig: {len(lost)} variable point(s) (e.g. id {min(lost)}) are observed in "
-                                      "registered images outside the config; COLMAP would add those observations with constant "
-                                      "poses -- add the images to the config with set_constant_cam_pose")
-        constant = set(cfg.constant_point3D_ids) | partly_outside
-        return _solve(rec, opts, cfg.image_ids, constant, sorted(cfg.constant_cam_poses), default_gauge=False)
+        constant = _config_constant_points(self.reconstruction, cfg)
+        return _solve(self.reconstruction, opts, cfg.image_ids, constant, sorted(cfg.constant_cam_poses), default_gauge=False)
 
     def solve(self, reconstruction):
         self.set_up_problem(reconstruction)
         return self._run(self.options.solver_options)
+
+
+def estimate_ba_covariance(reconstruction, options=None, config=None):
+    """Covariance of the bundle adjustment of `reconstruction` at its current state, on the GPU (``vggsfm_amd.ba.
+    estimate_covariance`` -> ``vggc_ba_covariance``): ``{"poses": {image_id: (6,6)}, "points": {point3D_id: (3,3)},
+    "variance_factor": float}`` as numpy arrays.  This is the project's OWN surface: pycolmap's namesake cannot be read here
+    (pycolmap is absent from the reference tree), so neither its signature nor its parametrisation is claimed.
+    Gauge and constants are those of the solve the same arguments would run: without `config` what ``bundle_adjustment``
+    fixes (all registered images, negative-depth observations left out, first image's pose and second image's t_x constant);
+    with a ``BundleAdjustmentConfig`` what ``BundleAdjuster(options, config)`` fixes (its images, constant poses and points).
+    Pose blocks are in the solver's tangent -- rotation (half the rotation vector of the left perturbation of cam_from_world),
+    then translation; constant ones are zero.  Points without a block in the problem (deleted, or fewer than two
+    observations) are left out.  The reconstruction is not changed."""
+    from . import ba as _ba
+    options = options or BundleAdjustmentOptions()
+    rec = reconstruction
+    if config is None:
+        ids, constant, pose_ids, default_gauge = None, None, None, True
+    else:
+        ids, constant = config.image_ids, _config_constant_points(rec, config)
+        pose_ids, default_gauge = sorted(config.constant_cam_poses), False
+    ids, pts, alive, ext, K, extra, tracks, masks, shared, model = rec.problem_arrays(ids)
+    cp = None
+    if constant is not None:
+        cp = np.zeros(len(pts), bool)
+        c = np.array(sorted(p for p in constant if 1 <= p <= len(pts)), dtype=np.int64)
+        cp[c - 1] = True
+    cov, valid_idx, deleted = _ba.covariance_of_call(
+        _dev(pts), _dev(ext), _dev(K), _dev(tracks, torch.float32), _dev(masks), None if extra is None else _dev(extra), shared,
+        model, options, constant_points=None if cp is None else _dev(cp),
+        constant_pose_frames=None if default_gauge else [ids.index(i) for i in pose_ids if i in ids],
+        filter_negative_depth=config is None)
+    pose = cov.pose.cpu().numpy()
+    blocks = cov.points.cpu().numpy()
+    vi, gone = valid_idx.cpu().numpy(), deleted.cpu().numpy()
+    return {"poses": {int(i): pose[r] for r, i in enumerate(ids)},
+            "points": {int(v) + 1: blocks[k] for k, v in enumerate(vi) if not gone[k]},
+            "variance_factor": cov.variance_factor}
 
 
 def _camera_params4(camera):
