@@ -10,7 +10,8 @@ header and one row in that table (tests/test_host_logic.py compares the two, typ
 ``SIGNATURES`` are a closed set; the multi-view entries (include/vggsfm_amd_multiview.h, prefix ``vggx_``) have the table
 ``SIGNATURES_MULTIVIEW``, applied next to the first, and the essential-matrix entries (include/vggsfm_amd_essential.h, prefix
 ``vgge_emat_``) the table ``SIGNATURES_ESSENTIAL``, and the EPnP entries (include/vggsfm_amd_pnp.h, prefix ``vggp_``) the table
-``SIGNATURES_PNP``, and the covariance entries (include/vggsfm_amd_covariance.h, prefix ``vggc_``) the table ``SIGNATURES_COV``.
+``SIGNATURES_PNP``, and the covariance entries (include/vggsfm_amd_covariance.h, prefix ``vggc_``) the table ``SIGNATURES_COV``,
+and the Sim(3) and pose-error entries (vggsfm_amd/csrc/vggsfm_amd_sim3.h, prefix ``vggs_``) the table ``SIGNATURES_SIM3``.
 """
 import ctypes
 import operator
@@ -197,6 +198,17 @@ SIGNATURES_COV = {
 EXPORTED_COV = list(SIGNATURES_COV)
 COV_CAMERAS, COV_POINTS = 1, 2      # VGGC_COV_* of the header
 
+# The sixth table: the vggs_* entries of vggsfm_amd/csrc/vggsfm_amd_sim3.h (csrc/sim3.hip, same library), in that header's
+# order.  tests/test_sim3_host.py compares the two.
+SIGNATURES_SIM3 = {
+    "vggs_sim3_workspace_bytes": (_SIZE, [_I, _I, _I]),
+    "vggs_sim3_fit": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "vggs_sim3_score": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "vggs_sim3_ransac": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "vggs_pose_pair_errors": (_INT, [_P, _P, _I, _P, _P, _P]),
+}
+EXPORTED_SIM3 = list(SIGNATURES_SIM3)
+
 _lib = None
 
 
@@ -224,7 +236,8 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL, SIGNATURES_PNP, SIGNATURES_COV):
+    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL, SIGNATURES_PNP, SIGNATURES_COV,
+                  SIGNATURES_SIM3):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -131,6 +131,40 @@ class Rigid3d:
         return self.rotation._R @ p + self.translation
 
 
+class Sim3d:
+    """pycolmap.Sim3d(scale, rotation, translation): x_new = scale * R x_old + t."""
+
+    def __init__(self, scale=1.0, rotation=None, translation=None):
+        self.scale = float(scale)
+        self.rotation = rotation if isinstance(rotation, Rotation3d) else Rotation3d(rotation)
+        self.translation = np.zeros(3) if translation is None else _np(translation).reshape(3).copy()
+
+    def matrix(self):
+        return np.concatenate([self.scale * self.rotation._R, self.translation[:, None]], axis=1)
+
+    def inverse(self):
+        Rt = self.rotation._R.T
+        return Sim3d(1.0 / self.scale, Rotation3d(Rt), -(Rt @ self.translation) / self.scale)
+
+    def __mul__(self, other):
+        if isinstance(other, Sim3d):
+            return Sim3d(self.scale * other.scale, Rotation3d(self.rotation._R @ other.rotation._R),
+                         self.scale * (self.rotation._R @ other.translation) + self.translation)
+        p = _np(other)
+        if p.ndim == 2:                                                    # (N,3) arrays row by row, as pycolmap
+            return self.scale * (p @ self.rotation._R.T) + self.translation
+        return self.scale * (self.rotation._R @ p) + self.translation
+
+    def transform_camera_world(self, cam_from_world):
+        """The pose, in the world this transform leads to, of a camera that keeps seeing what it saw (COLMAP
+        TransformCameraWorld): rotation R_c R^T, translation scale * t_c - R_c R^T t."""
+        rot = cam_from_world.rotation._R @ self.rotation._R.T
+        return Rigid3d(Rotation3d(rot), self.scale * cam_from_world.translation - rot @ self.translation)
+
+    def __repr__(self):
+        return f"Sim3d(scale={self.scale:.6g}, rotation_xyzw={self.rotation.quat.tolist()}, translation={self.translation.tolist()})"
+
+
 # ----------------------------------------------------------------------------------------------- camera
 class Camera:
     """pycolmap.Camera for the two models the reference supports (SIMPLE_PINHOLE f,cx,cy; SIMPLE_RADIAL f,cx,cy,k)."""
@@ -808,6 +842,14 @@ class Reconstruction:
         for k, i in enumerate(ids):
             self.images[i].cam_from_world = Rigid3d(Rotation3d(ext2[k, :, :3]), ext2[k, :, 3])
 
+    def transform(self, new_from_old_world):
+        """``Reconstruction::Transform`` (COLMAP 3.10): every point and every image pose move to the world of the
+        :class:`Sim3d`; reprojections do not change.  Host arrays, like :meth:`normalize`."""
+        alive = self._alive[:self._n]
+        self._xyz[:self._n][alive] = new_from_old_world * self._xyz[:self._n][alive]
+        for im in self.images.values():
+            im.cam_from_world = new_from_old_world.transform_camera_world(im.cam_from_world)
+
     # ---- the flat problem the solvers take
     def problem_arrays(self, image_ids=None):
         """(image_ids, points (n,3), alive (n,), extrinsics (S,3,4), K (S,3,3), extra (S,1)|None, tracks (S,n,2) f64,
@@ -1227,6 +1269,101 @@ class ObservationManager:
         rec._tracks = None
         rec._delete_points(np.nonzero(alive & ~keep)[0] + 1)
         return before - int((inl & keep[None]).sum())
+
+
+# ----------------------------------------------------------------------------------------------- Sim(3) alignment
+def _sim3d_result(out):
+    scale, R, t, num, inl, ok = (x.cpu().numpy() for x in out[:6])
+    if not bool(ok):
+        return None
+    return {"tgt_from_src": Sim3d(float(scale), Rotation3d(R), t), "num_inliers": int(num), "inliers": inl.astype(bool)}
+
+
+def estimate_sim3d(src, tgt):
+    """pycolmap.estimate_sim3d: least-squares Sim(3) with tgt ~ s R src + t over (N,3) point arrays (vggs_sim3_fit).
+    Returns {"tgt_from_src": Sim3d} or None when the points determine none."""
+    from . import sim3
+    scale, R, t, ok = sim3.estimate_sim3(_dev(_np(src).reshape(-1, 3)), _dev(_np(tgt).reshape(-1, 3)))
+    if not bool(ok.cpu()):
+        return None
+    return {"tgt_from_src": Sim3d(float(scale.cpu()), Rotation3d(R.cpu().numpy()), t.cpu().numpy())}
+
+
+def estimate_sim3d_robust(src, tgt, ransac_options=None, samples=None):
+    """pycolmap.estimate_sim3d_robust: 3-point LO-RANSAC (vggs_sim3_ransac) with ransac_options.max_error in the
+    target's units, .num_hypotheses samples (numpy's global RNG, or `samples` (H,3)) and .lo_max_rounds rounds of local
+    optimisation.  Returns {"tgt_from_src", "num_inliers", "inliers"} or None."""
+    from . import sim3
+    opts = ransac_options if ransac_options is not None else RANSACOptions(lo_max_rounds=10)     # (COLMAP's LO-RANSAC)
+    src, tgt = _np(src).reshape(-1, 3), _np(tgt).reshape(-1, 3)
+    if len(src) < 3:
+        return None
+    out = sim3.estimate_sim3_robust(_dev(src), _dev(tgt), float(opts.max_error), num_hypotheses=int(getattr(opts, "num_hypotheses", 1024)),
+                                    lo_rounds=int(getattr(opts, "lo_max_rounds", 10)), samples=samples)
+    res = _sim3d_result(out)
+    ratio = float(getattr(opts, "min_inlier_ratio", 0.0))
+    if res is not None and res["num_inliers"] < ratio * len(src):
+        return None
+    return res
+
+
+def align_reconstructions_via_proj_centers(src_reconstruction, tgt_reconstruction, max_proj_center_error, samples=None):
+    """pycolmap.align_reconstructions_via_proj_centers: the robust Sim(3) between the projection centres of the images
+    registered in both models (matched by name).  Returns the Sim3d tgt_from_src or None."""
+    by_name = {tgt_reconstruction.images[i].name: i for i in tgt_reconstruction.reg_image_ids()}
+    pairs = [(i, by_name[src_reconstruction.images[i].name]) for i in src_reconstruction.reg_image_ids()
+             if src_reconstruction.images[i].name in by_name]
+    if len(pairs) < 3:
+        return None
+    cs = np.stack([src_reconstruction.images[i].projection_center() for i, _ in pairs])
+    ct = np.stack([tgt_reconstruction.images[j].projection_center() for _, j in pairs])
+    opts = RANSACOptions(max_error=float(max_proj_center_error), lo_max_rounds=10)
+    res = estimate_sim3d_robust(cs, ct, opts, samples=samples)
+    return None if res is None else res["tgt_from_src"]
+
+
+def common_point_votes(src_reconstruction, tgt_reconstruction, min_common_observations=3):
+    """(src point ids, tgt point ids): for each source point the target point it shares the most observations with (same
+    image name, same point2D_idx), at least min_common_observations of them, ties to the smaller target id."""
+    by_name = {im.name: i for i, im in tgt_reconstruction.images.items()}
+    ptr, img, idx = src_reconstruction._track_csr()
+    src_pid = np.repeat(np.arange(1, len(ptr)), np.diff(ptr))
+    tgt_pid = np.full(len(img), -1, np.int64)
+    for i in np.unique(img):
+        j = by_name.get(src_reconstruction.images[int(i)].name)
+        if j is None:
+            continue
+        sel = np.nonzero(img == i)[0]
+        p2 = tgt_reconstruction.images[j].points2D._pid
+        ok = idx[sel] < len(p2)
+        pid = p2[idx[sel][ok]]
+        live = (pid >= 1) & (pid <= tgt_reconstruction._n)
+        live[live] = tgt_reconstruction._alive[pid[live] - 1]
+        tgt_pid[sel[ok][live]] = pid[live]
+    keep = tgt_pid >= 0
+    pairs, votes = np.unique(np.stack([src_pid[keep], tgt_pid[keep]], axis=1), axis=0, return_counts=True)
+    if len(pairs) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    order = np.lexsort((pairs[:, 1], -votes, pairs[:, 0]))        # per source id: most votes first, then the smaller target id
+    pairs, votes = pairs[order], votes[order]
+    first = np.concatenate([[True], pairs[1:, 0] != pairs[:-1, 0]])
+    sel = first & (votes >= min_common_observations)
+    return pairs[sel, 0], pairs[sel, 1]
+
+
+def align_reconstructions_via_points(src_reconstruction, tgt_reconstruction, min_common_observations=3, max_error=0.005,
+                                     min_inlier_ratio=0.9, samples=None):
+    """pycolmap.align_reconstructions_via_points: the robust Sim(3) between the 3D points the two models share
+    (`common_point_votes`).  Returns the Sim3d tgt_from_src, or None when fewer than min_inlier_ratio of the common
+    points agree."""
+    ps, pt = common_point_votes(src_reconstruction, tgt_reconstruction, min_common_observations)
+    if len(ps) < 3:
+        return None
+    opts = RANSACOptions(max_error=float(max_error), lo_max_rounds=10)
+    res = estimate_sim3d_robust(src_reconstruction._xyz[ps - 1], tgt_reconstruction._xyz[pt - 1], opts, samples=samples)
+    if res is None or res["num_inliers"] < min_inlier_ratio * len(ps):
+        return None
+    return res["tgt_from_src"]
 
 
 # ----------------------------------------------------------------------------------------------- module registration
