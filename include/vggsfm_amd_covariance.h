@@ -6,8 +6,8 @@
  *   absent from the reference tree -- no parity is claimed].  DESIGN.md section 19.
  *
  * Conventions of include/vggsfm_amd.h hold: device pointers, `stream` a hipStream_t as void*, no allocation, VGG_OK (0) or a
- * negative VGG_ERR_* code.  The names carry the prefix vggc_: the four earlier headers and their tables in vggsfm_amd/_lib.py
- * stay the closed sets they are; these entries have the table SIGNATURES_COV.  All arithmetic is float64 without
+ * negative VGG_ERR_* code.  The names carry the prefix vggc_; their rows in vggsfm_amd/_lib.py stand under this
+ * header's key of HEADERS.  All arithmetic is float64 without
  * floating-point contraction, every sum in a fixed order, no atomics: two calls on the same input give the same bits.
  * Every entry checks its sizes before it launches: a negative size, or NULL where data is required, is
  * VGG_ERR_INVALID_ARGUMENT; a size beyond what the index arithmetic holds is VGG_ERR_UNSUPPORTED; a workspace that is too

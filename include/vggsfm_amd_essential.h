@@ -6,8 +6,8 @@
  *   null_to_Nister_solution   vggsfm/two_view_geo/essential.py:271-488
  *
  * Conventions of include/vggsfm_amd.h hold: device pointers, `stream` a hipStream_t as void*, asynchronous, no
- * allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vgge_emat_: the two earlier headers and
- * their tables in vggsfm_amd/_lib.py stay the closed sets they are; these entries have the table SIGNATURES_ESSENTIAL.
+ * allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vgge_emat_; their rows in
+ * vggsfm_amd/_lib.py stand under this header's key of HEADERS.
  * All arithmetic is float64 without floating-point contraction, no transcendental functions, every sum in a fixed
  * order: a result is a function of its own (pair, sample) alone, whatever else is in the launch.
  *

@@ -9,10 +9,9 @@
  *   local_refinement_tri                        vggsfm/utils/triangulation_helpers.py:648-725
  *   triangulate_multi_view_point_from_tracks    vggsfm/utils/triangulation.py:650-674
  * Conventions of include/vggsfm_amd.h hold: device pointers, `stream` a hipStream_t as void*, asynchronous, no
- * allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vggx_: include/vggsfm_amd.h and its
- * table in vggsfm_amd/_lib.py stay the closed set they are; these entries have a table of their own there
- * (SIGNATURES_MULTIVIEW).  All arithmetic is float64, compiled without floating-point contraction; no floating-point
- * atomics: every result is a function of its own point alone, whatever else is in the launch.
+ * allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vggx_; their rows in
+ * vggsfm_amd/_lib.py stand under this header's key of HEADERS.  All arithmetic is float64, compiled without
+ * floating-point contraction; no floating-point atomics: every result is a function of its own point alone, whatever else is in the launch.
  *
  * "Problem" q of n: one DLT solve.  Its cameras and observations belong to group q / group_div; with cam_groups == 1 all
  * problems share ONE camera set (S,3,4) (wave-uniform loads), otherwise cams is (cam_groups,S,3,4) and

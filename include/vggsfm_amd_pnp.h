@@ -6,8 +6,8 @@
  *   model of each virtual frame of vgg_p3p_ransac
  *
  * Conventions of include/vggsfm_amd.h hold: device pointers, `stream` a hipStream_t as void*, asynchronous, no
- * allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vggp_: the three earlier headers and
- * their tables in vggsfm_amd/_lib.py stay the closed sets they are; these entries have the table SIGNATURES_PNP.
+ * allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vggp_; their rows in
+ * vggsfm_amd/_lib.py stand under this header's key of HEADERS.
  * All arithmetic is float64 without floating-point contraction, no transcendental functions, every sum in a fixed
  * order, no atomics: a result is a function of its own problem alone, whatever else is in the launch.  One workgroup of
  * 256 threads per problem.

@@ -6,9 +6,8 @@
  *   (camera_to_rel_deg: rotation_angle, translation_angle, compare_translation_by_angle).
  *
  * Conventions of include/vggsfm_amd.h hold: device pointers, `stream` a hipStream_t as void*, asynchronous (no entry
- * synchronises with the host), no allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vggs_:
- * the five earlier headers and their tables in vggsfm_amd/_lib.py stay the closed sets they are; these entries have the
- * table SIGNATURES_SIM3.  This header lives beside the kernels, not under include/.
+ * synchronises with the host), no allocation, VGG_OK (0) or a negative VGG_ERR_* code.  The names carry the prefix vggs_;
+ * their rows in vggsfm_amd/_lib.py stand under this header's key of HEADERS.
  *
  * A transform is 13 doubles: s, R row-major (9), t (3), with  tgt ~ s R src + t.  Point data is float64, masks are uint8.
  * All arithmetic is float64 without floating-point contraction; every sum is taken in a fixed order (block trees and

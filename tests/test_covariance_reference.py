@@ -1,16 +1,12 @@
 """The bundle adjustment covariance, the part that needs no GPU: the long-double reference of tests/covariance_cases.py by its
 two routes (dense inverse of the whole J^T J against the Schur route) and the float64 deviation that sets the GPU tests' bounds;
-the fifth header against the fifth binding table and the library's symbols; argument validation before any launch; the host
-mapping (camera order undone, column labels).
+argument validation before any launch; the host mapping (camera order undone, column labels).
 
 Agreement of the two routes: both are long-double evaluations of the same quantity, so they may differ by what long-double
 rounding does to either -- the float64 deviation of the case scaled by the ratio of the unit roundoffs, 2^-11 (64-bit against
 53-bit significands) -- and the bound is 100 x that, at least 1e-16.  The measured figures are in covariance_cases' docstring."""
 import ctypes
 import inspect
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,12 +14,9 @@ import torch
 
 from tests import ba_system_cases as SC
 from tests import covariance_cases as CC
-from tests.test_host_logic import _c_kind, _parse_header
 from vggsfm_amd import _lib
 from vggsfm_amd import ba as BA
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EARLIER_HEADERS = ("vggsfm_amd.h", "vggsfm_amd_multiview.h", "vggsfm_amd_essential.h", "vggsfm_amd_pnp.h")
 
 
 @pytest.mark.parametrize("name", CC.CASES)
@@ -78,49 +71,6 @@ def test_cholesky_inverse_is_an_inverse():
         assert np.abs((A.astype(CC.LD) @ ref - np.eye(n)).astype(np.float64)).max() < 1e-13
         assert dev < 1e-11 and bound >= SC.FLOOR_STEP
         assert (A == A.T).all() and np.linalg.cond(A) < 1e8
-
-
-# --- C-ABI -----------------------------------------------------------------------------------------------------------
-def _parse_cov_header():
-    src = open(os.path.join(ROOT, "include", "vggsfm_amd_covariance.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
-    return {name: (_c_kind(ret), [_c_kind(p) for p in params.split(",") if p.strip() != "void"])
-            for ret, name, params in re.findall(r"([\w\s*]+?)\b(vggc_\w+)\s*\(([^)]*)\)\s*;", src)}
-
-
-def test_fifth_header_table_and_symbols_agree():
-    functions = _parse_cov_header()
-    assert len(functions) == 4
-    restype_kind = {ctypes.c_int: "int", ctypes.c_size_t: "size_t"}
-    native = {ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_int: "int"}
-    table = {name: (restype_kind[res], [getattr(a, "kind", None) or native[a] for a in args])
-             for name, (res, args) in _lib.SIGNATURES_COV.items()}
-    assert list(table) == list(functions) == _lib.EXPORTED_COV                 # same names, in the header's order
-    for name in functions:
-        assert table[name] == functions[name], name
-    assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r" T (vggc_\w+)$", nm, flags=re.M)) == set(functions)
-    # the closed sets do not know the new entries
-    first, _ = _parse_header(open(os.path.join(ROOT, "include", "vggsfm_amd.h")).read())
-    assert set(first) == set(_lib.SIGNATURES) and not set(first) & set(functions)
-    for other in (_lib.SIGNATURES, _lib.SIGNATURES_MULTIVIEW, _lib.SIGNATURES_ESSENTIAL, _lib.SIGNATURES_PNP):
-        assert not set(other) & set(functions)
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.SIGNATURES_COV.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
-    src = open(os.path.join(ROOT, "include", "vggsfm_amd_covariance.h")).read()
-    assert (int(re.search(r"#define VGGC_COV_CAMERAS (\d+)", src).group(1)), int(re.search(r"#define VGGC_COV_POINTS (\d+)", src).group(1))) \
-        == (_lib.COV_CAMERAS, _lib.COV_POINTS)
-    assert L.vgg_abi_version() == 2                                            # no struct changed
-
-
-def test_no_other_header_names_the_prefix():
-    for header in EARLIER_HEADERS:
-        assert "vggc_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    assert sorted(os.listdir(os.path.join(ROOT, "include"))) == sorted(EARLIER_HEADERS + ("vggsfm_amd_covariance.h",))
 
 
 def _host_problem(name="a"):

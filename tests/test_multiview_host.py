@@ -1,22 +1,18 @@
 """Masked multi-view triangulation, the part that needs no GPU: a numpy restatement of every function against every golden
-on the admitted set (bounds: tests/multiview_cases.py), the admission caps on the committed files, the second header against
-the second binding table and the library's symbols, and the error paths."""
+on the admitted set (bounds: tests/multiview_cases.py), the admission caps on the committed files, the host-only entry logic
+and the error paths."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import multiview_cases as MC
-from tests.test_host_logic import _c_kind, _parse_header
 from vggsfm_amd import _lib
 from vggsfm_amd.utils import triangulation as TR
 from vggsfm_amd.utils import triangulation_helpers as TH
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_every_golden_file_is_known_and_small():
@@ -94,39 +90,6 @@ def test_numpy_restatement_of_the_angular_error():
         # (degrees are held to the bound in degrees, radians to the same number in radians: the tighter of the two)
         MC.assert_close(f"numpy angerr deg={deg}", {"angles": da, "cosines": dc})
         assert c.max() <= 1.0 and a.shape == (4, 6, 50)
-
-
-# --- C-ABI -----------------------------------------------------------------------------------------------------------
-def _parse_multiview_header():
-    src = open(os.path.join(ROOT, "include", "vggsfm_amd_multiview.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
-    return {name: (_c_kind(ret), [_c_kind(p) for p in params.split(",") if p.strip() != "void"])
-            for ret, name, params in re.findall(r"([\w\s*]+?)\b(vggx_\w+)\s*\(([^)]*)\)\s*;", src)}
-
-
-def test_second_header_table_and_symbols_agree():
-    functions = _parse_multiview_header()
-    assert len(functions) == 7
-    restype_kind = {ctypes.c_char_p: "pointer", ctypes.c_int: "int", ctypes.c_size_t: "size_t"}
-    native = {ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_int: "int"}
-    table = {name: (restype_kind[res], [getattr(a, "kind", None) or native[a] for a in args])
-             for name, (res, args) in _lib.SIGNATURES_MULTIVIEW.items()}
-    assert list(table) == list(functions) == _lib.EXPORTED_MULTIVIEW          # same names, in the header's order
-    for name in functions:
-        assert table[name] == functions[name], name
-    assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r" T (vggx_\w+)$", nm, flags=re.M)) == set(functions)
-    # the first table still equals the first header, and neither knows the new entries
-    first, _ = _parse_header(open(os.path.join(ROOT, "include", "vggsfm_amd.h")).read())
-    assert set(first) == set(_lib.SIGNATURES) and not set(first) & set(functions)
-    assert not any(n.startswith("vggx_") for n in _lib.SIGNATURES) and "vggx_" not in open(
-        os.path.join(ROOT, "include", "vggsfm_amd.h")).read()
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.SIGNATURES_MULTIVIEW.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
 
 
 def test_host_only_entry_logic():

@@ -1,11 +1,8 @@
-"""EPnP and the local optimisation of the P3P RANSAC, the part that needs no GPU: the fourth header against the fourth
-binding table and the library's symbols, argument validation before any launch, the CPU yardstick of tests/pnp_cases.py
-checked by itself against the golden file made from the reference's own ``efficient_pnp`` (and the golden file against the
+"""EPnP and the local optimisation of the P3P RANSAC, the part that needs no GPU: argument validation before any launch, the CPU
+yardstick of tests/pnp_cases.py checked by itself against the golden file made from the reference's own ``efficient_pnp`` (and the golden file against the
 reference where its tree exists), the restated LO loop on the LO scene, and the opt-in switch."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,48 +10,11 @@ import torch
 
 from oracle import ref_harness
 from tests import pnp_cases as PC
-from tests.test_host_logic import _c_kind, _parse_header
 from vggsfm_amd import _lib, ba_options, pose
 from vggsfm_amd import two_view_geo as TV
 from vggsfm_amd.two_view_geo import perspective_n_points as PN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ("vggsfm_amd.h", "vggsfm_amd_multiview.h", "vggsfm_amd_essential.h", "vggsfm_amd_pnp.h")
-
-
-# --- C-ABI -----------------------------------------------------------------------------------------------------------
-def _parse_pnp_header():
-    src = open(os.path.join(ROOT, "include", "vggsfm_amd_pnp.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
-    return {name: (_c_kind(ret), [_c_kind(p) for p in params.split(",") if p.strip() != "void"])
-            for ret, name, params in re.findall(r"([\w\s*]+?)\b(vggp_\w+)\s*\(([^)]*)\)\s*;", src)}
-
-
-def test_fourth_header_table_and_symbols_agree():
-    functions = _parse_pnp_header()
-    assert len(functions) == 3
-    restype_kind = {ctypes.c_int: "int", ctypes.c_size_t: "size_t"}
-    native = {ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_int: "int"}
-    table = {name: (restype_kind[res], [getattr(a, "kind", None) or native[a] for a in args])
-             for name, (res, args) in _lib.SIGNATURES_PNP.items()}
-    assert list(table) == list(functions) == _lib.EXPORTED_PNP                 # same names, in the header's order
-    for name in functions:
-        assert table[name] == functions[name], name
-    assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r" T (vggp_\w+)$", nm, flags=re.M)) == set(functions)
-    # the three closed sets do not know the new entries
-    first, _ = _parse_header(open(os.path.join(ROOT, "include", "vggsfm_amd.h")).read())
-    assert set(first) == set(_lib.SIGNATURES) and not set(first) & set(functions)
-    for other in (_lib.SIGNATURES, _lib.SIGNATURES_MULTIVIEW, _lib.SIGNATURES_ESSENTIAL):
-        assert not set(other) & set(functions)
-    for header in HEADERS[:3]:
-        assert "vggp_" not in open(os.path.join(ROOT, "include", header)).read()
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.SIGNATURES_PNP.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
 
 
 def test_entries_refuse_bad_sizes_before_any_launch():

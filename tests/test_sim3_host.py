@@ -1,58 +1,18 @@
-"""Sim(3) alignment and pose metrics, the part that needs no GPU: the sixth header (beside the kernels, not under
-include/) against the sixth binding table and the library's symbols, argument validation before any launch, the Sim3d
-algebra, Reconstruction.transform and the shared-observation vote of align_reconstructions_via_points."""
+"""Sim(3) alignment and pose metrics, the part that needs no GPU: argument validation before any launch, the Sim3d algebra,
+Reconstruction.transform and the shared-observation vote of align_reconstructions_via_points."""
 import copy
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import sim3_cases as SC
-from tests.test_host_logic import _c_kind
 from vggsfm_amd import _lib, sim3, video
 from vggsfm_amd import pycolmap_compat as pc
 from vggsfm_amd.scene import make_scene
 from vggsfm_amd.utils import metric
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "vggsfm_amd", "csrc", "vggsfm_amd_sim3.h")
-
-
-def _parse_sim3_header():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
-    return {name: (_c_kind(ret), [_c_kind(p) for p in params.split(",") if p.strip() != "void"])
-            for ret, name, params in re.findall(r"([\w\s*]+?)\b(vggs_\w+)\s*\(([^)]*)\)\s*;", src)}
-
-
-def test_sixth_header_table_and_symbols_agree():
-    functions = _parse_sim3_header()
-    assert len(functions) == 5
-    restype_kind = {ctypes.c_int: "int", ctypes.c_size_t: "size_t"}
-    native = {ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_int: "int"}
-    table = {name: (restype_kind[res], [getattr(a, "kind", None) or native[a] for a in args])
-             for name, (res, args) in _lib.SIGNATURES_SIM3.items()}
-    assert list(table) == list(functions) == _lib.EXPORTED_SIM3               # same names, in the header's order
-    for name in functions:
-        assert table[name] == functions[name], name
-    assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r" T (vggs_\w+)$", nm, flags=re.M)) == set(functions)
-    # no other table and no header under include/ knows the prefix
-    for other in (_lib.SIGNATURES, _lib.SIGNATURES_MULTIVIEW, _lib.SIGNATURES_ESSENTIAL, _lib.SIGNATURES_PNP, _lib.SIGNATURES_COV):
-        assert not set(other) & set(functions)
-    for header in os.listdir(os.path.join(ROOT, "include")):
-        assert "vggs_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    L = _lib.lib()
-    assert L.vgg_abi_version() == 2 == _lib.ABI_VERSION
-    for name, (restype, argtypes) in _lib.SIGNATURES_SIM3.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
 
 
 def test_entries_refuse_bad_sizes_before_any_launch():

@@ -1,17 +1,13 @@
-"""ctypes binding of the C-ABI in include/vggsfm_amd.h (libvggsfm_amd.so, built for gfx950).
+"""ctypes binding of the C-ABI in the headers under include/ (libvggsfm_amd.so, built for gfx950).
 
 There is NO fallback: if the shared library is missing or was built for another target, importing
 a product function that needs it raises.  torch is imported first so that the library resolves
 ``libamdhip64.so.7`` to the HIP runtime torch already loaded (same streams, same allocations).
 
-The C type of every argument of every entry is declared once, in ``SIGNATURES`` below, and applied when the library is
-loaded: callers pass tensors, ``None``, ints and floats as they are.  A new C-ABI entry needs one prototype in the
-header and one row in that table (tests/test_host_logic.py compares the two, type by type).  include/vggsfm_amd.h and
-``SIGNATURES`` are a closed set; the multi-view entries (include/vggsfm_amd_multiview.h, prefix ``vggx_``) have the table
-``SIGNATURES_MULTIVIEW``, applied next to the first, and the essential-matrix entries (include/vggsfm_amd_essential.h, prefix
-``vgge_emat_``) the table ``SIGNATURES_ESSENTIAL``, and the EPnP entries (include/vggsfm_amd_pnp.h, prefix ``vggp_``) the table
-``SIGNATURES_PNP``, and the covariance entries (include/vggsfm_amd_covariance.h, prefix ``vggc_``) the table ``SIGNATURES_COV``,
-and the Sim(3) and pose-error entries (vggsfm_amd/csrc/vggsfm_amd_sim3.h, prefix ``vggs_``) the table ``SIGNATURES_SIM3``.
+The C type of every argument of every entry is declared once, in ``HEADERS`` below: one row per entry, grouped by the public
+header that declares it, and applied when the library is loaded, so callers pass tensors, ``None``, ints and floats as they
+are.  A new C-ABI entry needs a prototype in a header under include/ and a row under that header's key
+(tests/test_c_abi.py compares the two, type by type, and both with the library's symbols).
 """
 import ctypes
 import operator
@@ -98,116 +94,99 @@ _I, _L, _Z, _U = (_integer(*kc) for kc in (("int", ctypes.c_int), ("long", ctype
                                             ("unsigned long long", ctypes.c_ulonglong)))
 _D, _INT, _SIZE = ctypes.c_double, ctypes.c_int, ctypes.c_size_t
 
-# name -> (return type, parameter types) of every function include/vggsfm_amd.h declares, in the header's order.
+# header under include/ -> {name: (return type, parameter types)} of every function it declares, in the header's order.
 # vgg_ba_phase, called four to eight times per LM iteration, has ctypes' own types: converted in C, at the price that its
 # caller wraps the workspace (_lib.ptr) and that an out-of-range phase number would be masked, not refused.
-SIGNATURES = {
-    "vgg_build_arch": (ctypes.c_char_p, []),
-    "vgg_abi_version": (_INT, []),
-    "vgg_abi_sizeof": (_SIZE, [_I]),
-    "vgg_project_points": (_INT, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
-    "vgg_filter_points_workspace_bytes": (_SIZE, [_I]),
-    "vgg_filter_points": (_INT, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _D, _D, _I, _D, _D, _P, _P, _P, _P]),
-    "vgg_cam_from_img_workspace_bytes": (_SIZE, [_I, _I, _I]),
-    "vgg_cam_from_img": (_INT, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _D, _D, _D, _P, _P, _P]),
-    "vgg_triangulate_chunks_workspace_bytes": (_SIZE, [_I, _I]),
-    "vgg_triangulate_tracks_chunks": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P]),
-    "vgg_triangulate_tracks_chunks_enqueue": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
-    "vgg_triangulate_by_pair": (_INT, [_P, _P, _I, _I, _P, _P]),
-    "vgg_triangulate_workspace_bytes": (_SIZE, [_I, _I, _I, _I]),
-    "vgg_triangulate_tracks": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P]),
-    "vgg_ba_workspace_bytes": (_SIZE, [_P, _P]),
-    "vgg_ba_solve": (_INT, [_P, _P, _P, _Z, _P, _P, _I, _P]),
-    "vgg_ba_begin": (_INT, [_P, _P, _P, _Z, _I, _I, _P]),
-    "vgg_ba_phase": (_INT, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    "vgg_ba_reduce_buffer": (_INT, [_P, _P, _P, _I, _P, _P]),
-    "vgg_ba_finish": (_INT, [_P, _P, _P, _P, _P, _I, _P]),
-    "vgg_ba_poll_done": (_INT, [_P, _P, _P, _P, _P]),
-    "vgg_pose_refine": (_INT, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _D, _P, _P]),
-    "vgg_p3p_ransac_workspace_bytes": (_SIZE, [_I, _I]),
-    "vgg_p3p_ransac": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "vgg_fmat_seven_point": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "vgg_fmat_score": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _P]),
-    "vgg_fmat_eight_point": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P]),
-    "vgg_fmat_residuals": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P]),
-    "vgg_ba_tuning": (_INT, [_I, _I, _I, _I]),
-    "vgg_ba_set_tile_rhs": (_INT, [_I]),
-    "vgg_ba_profile": (_INT, [_I, _I]),
-    "vgg_ba_profile_read": (_INT, [_I, _P, _P, _I]),
-    "vgg_cholesky_workspace_bytes": (_SIZE, [_I]),
-    "vgg_cholesky_solve": (_INT, [_P, _P, _I, _P, _P, _P]),
-    "vgg_cholesky_solve_split": (_INT, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "vgg_cholesky_solve_envelope": (_INT, [_P, _P, _I, _P, _P, _P, _P]),
-    "vgg_sparse_depth": (_INT, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P]),
-    "vgg_depth_align_workspace_bytes": (_SIZE, [_L]),
-    "vgg_depth_align": (_INT, [_P, _P, _P, _P, _P, _P, _I, _L, _P, _I, _U, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "vgg_depth_apply": (_INT, [_P, _P, _P, _P, _P, _I, _L, _P, _P, _P]),
-    "vgg_depth_unproject": (_INT, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
-    "vgg_reproj_stats_workspace_bytes": (_SIZE, [_L]),
-    "vgg_reproj_stats": (_INT, [_P, _P, _L, _I, _P, _P, _Z, _P]),
-    "vgg_reproj_visible": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "vgg_reproj_draw": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "vgg_color_gather": (_INT, [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P, _P, _P]),
-    "vgg_color_reduce": (_INT, [_P, _L, _L, _P, _P, _P, _P, _P]),
-    "vgg_track_owner": (_INT, [_P, _I, _P, _I, _I, _I, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
-    "vgg_track_resolve": (_INT, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+HEADERS = {
+    "vggsfm_amd.h": {
+        "vgg_build_arch": (ctypes.c_char_p, []),
+        "vgg_abi_version": (_INT, []),
+        "vgg_abi_sizeof": (_SIZE, [_I]),
+        "vgg_project_points": (_INT, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
+        "vgg_filter_points_workspace_bytes": (_SIZE, [_I]),
+        "vgg_filter_points": (_INT, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _D, _D, _I, _D, _D, _P, _P, _P, _P]),
+        "vgg_cam_from_img_workspace_bytes": (_SIZE, [_I, _I, _I]),
+        "vgg_cam_from_img": (_INT, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _D, _D, _D, _P, _P, _P]),
+        "vgg_triangulate_chunks_workspace_bytes": (_SIZE, [_I, _I]),
+        "vgg_triangulate_tracks_chunks": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P]),
+        "vgg_triangulate_tracks_chunks_enqueue": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
+        "vgg_triangulate_by_pair": (_INT, [_P, _P, _I, _I, _P, _P]),
+        "vgg_triangulate_workspace_bytes": (_SIZE, [_I, _I, _I, _I]),
+        "vgg_triangulate_tracks": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P]),
+        "vgg_ba_workspace_bytes": (_SIZE, [_P, _P]),
+        "vgg_ba_solve": (_INT, [_P, _P, _P, _Z, _P, _P, _I, _P]),
+        "vgg_ba_begin": (_INT, [_P, _P, _P, _Z, _I, _I, _P]),
+        "vgg_ba_phase": (_INT, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+        "vgg_ba_reduce_buffer": (_INT, [_P, _P, _P, _I, _P, _P]),
+        "vgg_ba_finish": (_INT, [_P, _P, _P, _P, _P, _I, _P]),
+        "vgg_ba_poll_done": (_INT, [_P, _P, _P, _P, _P]),
+        "vgg_pose_refine": (_INT, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _D, _P, _P]),
+        "vgg_p3p_ransac_workspace_bytes": (_SIZE, [_I, _I]),
+        "vgg_p3p_ransac": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+        "vgg_fmat_seven_point": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+        "vgg_fmat_score": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _P]),
+        "vgg_fmat_eight_point": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P]),
+        "vgg_fmat_residuals": (_INT, [_P, _P, _P, _P, _I, _I, _P, _P]),
+        "vgg_ba_tuning": (_INT, [_I, _I, _I, _I]),
+        "vgg_ba_set_tile_rhs": (_INT, [_I]),
+        "vgg_ba_profile": (_INT, [_I, _I]),
+        "vgg_ba_profile_read": (_INT, [_I, _P, _P, _I]),
+        "vgg_cholesky_workspace_bytes": (_SIZE, [_I]),
+        "vgg_cholesky_solve": (_INT, [_P, _P, _I, _P, _P, _P]),
+        "vgg_cholesky_solve_split": (_INT, [_P, _P, _I, _I, _I, _P, _P, _P]),
+        "vgg_cholesky_solve_envelope": (_INT, [_P, _P, _I, _P, _P, _P, _P]),
+        "vgg_sparse_depth": (_INT, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P]),
+        "vgg_depth_align_workspace_bytes": (_SIZE, [_L]),
+        "vgg_depth_align": (_INT, [_P, _P, _P, _P, _P, _P, _I, _L, _P, _I, _U, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+        "vgg_depth_apply": (_INT, [_P, _P, _P, _P, _P, _I, _L, _P, _P, _P]),
+        "vgg_depth_unproject": (_INT, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+        "vgg_reproj_stats_workspace_bytes": (_SIZE, [_L]),
+        "vgg_reproj_stats": (_INT, [_P, _P, _L, _I, _P, _P, _Z, _P]),
+        "vgg_reproj_visible": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+        "vgg_reproj_draw": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+        "vgg_color_gather": (_INT, [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P, _P, _P]),
+        "vgg_color_reduce": (_INT, [_P, _L, _L, _P, _P, _P, _P, _P]),
+        "vgg_track_owner": (_INT, [_P, _I, _P, _I, _I, _I, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
+        "vgg_track_resolve": (_INT, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    },
+    "vggsfm_amd_multiview.h": {         # csrc/multiview.hip
+        "vggx_multiview_workspace_bytes": (_SIZE, [_L, _I]),
+        "vggx_view_centers": (_INT, [_P, _L, _P, _P]),
+        "vggx_multiview_triangulate": (_INT, [_P, _L, _I, _P, _I, _L, _L, _P, _I, _L, _L, _P, _L, _I, _I, _I, _D, _P, _P, _P, _P,
+                                              _P, _P]),
+        "vggx_max_tri_angle": (_INT, [_P, _L, _I, _P, _L, _I, _I, _D, _P, _P, _P, _P]),
+        "vggx_tri_angle_table": (_INT, [_P, _L, _P, _L, _I, _D, _P, _P, _P]),
+        "vggx_tri_angle_pairs": (_INT, [_P, _P, _L, _P, _L, _D, _P, _P]),
+        "vggx_angular_error": (_INT, [_P, _P, _P, _L, _L, _L, _I, _P, _P, _P]),
+    },
+    "vggsfm_amd_essential.h": {         # csrc/essential.hip
+        "vgge_emat_five_point": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+        "vgge_emat_solve": (_INT, [_P, _P, _P, _L, _I, _P, _P, _P]),
+        "vgge_emat_score": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+        "vgge_emat_refine": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    },
+    "vggsfm_amd_pnp.h": {               # csrc/epnp.hip
+        "vggp_epnp_solve": (_INT, [_P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+        "vggp_pose_score": (_INT, [_P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
+        "vggp_epnp_lo": (_INT, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
+    },
+    "vggsfm_amd_sim3.h": {              # csrc/sim3.hip
+        "vggs_sim3_workspace_bytes": (_SIZE, [_I, _I, _I]),
+        "vggs_sim3_fit": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+        "vggs_sim3_score": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+        "vggs_sim3_ransac": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+        "vggs_pose_pair_errors": (_INT, [_P, _P, _I, _P, _P, _P]),
+    },
+    "vggsfm_amd_covariance.h": {        # csrc/covariance.hip
+        "vggc_spd_inverse_workspace_bytes": (_SIZE, [_I]),
+        "vggc_spd_inverse": (_INT, [_P, _I, _P, _P, _P]),
+        "vggc_ba_covariance_workspace_bytes": (_SIZE, [_P, _P, _I]),
+        "vggc_ba_covariance": (_INT, [_P, _P, _P, _Z, _I, _P, _P, _P, _P, _P, _P, _P]),
+    },
 }
+SIGNATURES = {name: row for table in HEADERS.values() for name, row in table.items()}
 EXPORTED = list(SIGNATURES)
-
-# The second table: the vggx_* entries of include/vggsfm_amd_multiview.h (csrc/multiview.hip, same library), in that header's
-# order.  tests/test_multiview_host.py compares it with that header as tests/test_host_logic.py compares the first.
-SIGNATURES_MULTIVIEW = {
-    "vggx_multiview_workspace_bytes": (_SIZE, [_L, _I]),
-    "vggx_view_centers": (_INT, [_P, _L, _P, _P]),
-    "vggx_multiview_triangulate": (_INT, [_P, _L, _I, _P, _I, _L, _L, _P, _I, _L, _L, _P, _L, _I, _I, _I, _D, _P, _P, _P, _P,
-                                          _P, _P]),
-    "vggx_max_tri_angle": (_INT, [_P, _L, _I, _P, _L, _I, _I, _D, _P, _P, _P, _P]),
-    "vggx_tri_angle_table": (_INT, [_P, _L, _P, _L, _I, _D, _P, _P, _P]),
-    "vggx_tri_angle_pairs": (_INT, [_P, _P, _L, _P, _L, _D, _P, _P]),
-    "vggx_angular_error": (_INT, [_P, _P, _P, _L, _L, _L, _I, _P, _P, _P]),
-}
-EXPORTED_MULTIVIEW = list(SIGNATURES_MULTIVIEW)
-
-# The third table: the vgge_emat_* entries of include/vggsfm_amd_essential.h (csrc/essential.hip, same library), in that
-# header's order.  tests/test_essential_host.py compares the two.
-SIGNATURES_ESSENTIAL = {
-    "vgge_emat_five_point": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "vgge_emat_solve": (_INT, [_P, _P, _P, _L, _I, _P, _P, _P]),
-    "vgge_emat_score": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "vgge_emat_refine": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-}
-EXPORTED_ESSENTIAL = list(SIGNATURES_ESSENTIAL)
-
-# The fourth table: the vggp_* entries of include/vggsfm_amd_pnp.h (csrc/epnp.hip, same library), in that header's order.
-# tests/test_pnp_host.py compares the two.
-SIGNATURES_PNP = {
-    "vggp_epnp_solve": (_INT, [_P, _I, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "vggp_pose_score": (_INT, [_P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
-    "vggp_epnp_lo": (_INT, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
-}
-EXPORTED_PNP = list(SIGNATURES_PNP)
-
-# The fifth table: the vggc_* entries of include/vggsfm_amd_covariance.h (csrc/covariance.hip, same library), in that header's
-# order.  tests/test_covariance_reference.py compares the two.
-SIGNATURES_COV = {
-    "vggc_spd_inverse_workspace_bytes": (_SIZE, [_I]),
-    "vggc_spd_inverse": (_INT, [_P, _I, _P, _P, _P]),
-    "vggc_ba_covariance_workspace_bytes": (_SIZE, [_P, _P, _I]),
-    "vggc_ba_covariance": (_INT, [_P, _P, _P, _Z, _I, _P, _P, _P, _P, _P, _P, _P]),
-}
-EXPORTED_COV = list(SIGNATURES_COV)
-COV_CAMERAS, COV_POINTS = 1, 2      # VGGC_COV_* of the header
-
-# The sixth table: the vggs_* entries of vggsfm_amd/csrc/vggsfm_amd_sim3.h (csrc/sim3.hip, same library), in that header's
-# order.  tests/test_sim3_host.py compares the two.
-SIGNATURES_SIM3 = {
-    "vggs_sim3_workspace_bytes": (_SIZE, [_I, _I, _I]),
-    "vggs_sim3_fit": (_INT, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "vggs_sim3_score": (_INT, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "vggs_sim3_ransac": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "vggs_pose_pair_errors": (_INT, [_P, _P, _I, _P, _P, _P]),
-}
-EXPORTED_SIM3 = list(SIGNATURES_SIM3)
+COV_CAMERAS, COV_POINTS = 1, 2      # VGGC_COV_* of include/vggsfm_amd_covariance.h
 
 _lib = None
 
@@ -236,11 +215,9 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for table in (SIGNATURES, SIGNATURES_MULTIVIEW, SIGNATURES_ESSENTIAL, SIGNATURES_PNP, SIGNATURES_COV,
-                  SIGNATURES_SIM3):
-        for name, (restype, argtypes) in table.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

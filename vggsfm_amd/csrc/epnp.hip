@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "two_view.hpp"
 #include "kabsch3.hpp"
+#include "support.hpp"
 #include "../../include/vggsfm_amd_pnp.h"
 
 namespace vgg {
@@ -374,19 +375,6 @@ __device__ __forceinline__ bool epnp_block(EpnpShared& sh, const double* x, cons
   return true;
 }
 
-// squared residual on the normalised plane and the support rule of p3p.hip
-__device__ __forceinline__ bool pnp_point_error(const double* P, double X0, double X1, double X2, double u, double w, double thr_sq,
-                                                double& e) {
-  const double px = ((P[0] * X0 + P[1] * X1) + P[2] * X2) + P[3];
-  const double py = ((P[4] * X0 + P[5] * X1) + P[6] * X2) + P[7];
-  const double pz = ((P[8] * X0 + P[9] * X1) + P[10] * X2) + P[11];
-  const bool front = pz > 1e-12;
-  const double zs = front ? pz : 1.0;
-  const double ex = px / zs - u, ey = py / zs - w;
-  e = ex * ex + ey * ey;
-  return front && e <= thr_sq;
-}
-
 // support of pose P (registers, the same in every thread) over the candidates of one frame; om: where to store the mask, or NULL
 __device__ __forceinline__ void score_block(double (*red)[256], const double* P, const double* xf, const double* X, const uint8_t* mf, int N,
                                    double thr_sq, uint8_t* om, int& count, double& sum) {
@@ -394,7 +382,7 @@ __device__ __forceinline__ void score_block(double (*red)[256], const double* P,
   for (int n = threadIdx.x; n < N; n += 256) {
     double e = 0.0;
     const bool in = (!mf || mf[n]) &&
-                    pnp_point_error(P, X[3 * (size_t)n], X[3 * (size_t)n + 1], X[3 * (size_t)n + 2], xf[2 * (size_t)n], xf[2 * (size_t)n + 1], thr_sq, e);
+                    point_error(P, X[3 * (size_t)n], X[3 * (size_t)n + 1], X[3 * (size_t)n + 2], xf[2 * (size_t)n], xf[2 * (size_t)n + 1], thr_sq, e);
     acc[0] = acc[0] + (in ? 1.0 : 0.0);
     acc[1] = acc[1] + (in ? e : 0.0);
     if (om) om[n] = in ? 1 : 0;

@@ -147,12 +147,6 @@ __device__ __forceinline__ int sturm_variations(const Sturm& S, double x) {
 }
 
 // ------------------------------------------------------------------------------------------------ 3x3 helpers
-__device__ __forceinline__ void mat3_ab(const double* A, const double* B, double* C) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
 __device__ __forceinline__ void mat3_abt(const double* A, const double* B, double* C) {
 #pragma unroll
   for (int i = 0; i < 3; ++i)

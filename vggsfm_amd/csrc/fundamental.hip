@@ -76,22 +76,15 @@ __device__ inline void cubic_real_roots(double c3, double c2, double c1, double 
 __device__ inline double det3(const double* F) {
   return (F[0] * (F[4] * F[8] - F[5] * F[7]) - F[1] * (F[3] * F[8] - F[5] * F[6])) + F[2] * (F[3] * F[7] - F[4] * F[6]);
 }
-// C = A B (3x3 row-major), terms added left to right
-__device__ inline void mat3(const double* A, const double* B, double* C) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
 // F = T2^T Fh T1 for T = [[s,0,a],[0,s,b],[0,0,1]] given as full 3x3, then unit Frobenius norm; returns the norm
 __device__ inline double denormalize_unit(const double* Fh, const double* T1, const double* T2, double* F) {
   double tmp[9], T2t[9];
-  mat3(Fh, T1, tmp);
+  mat3_ab(Fh, T1, tmp);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) T2t[3 * i + j] = T2[3 * j + i];
-  mat3(T2t, tmp, F);
+  mat3_ab(T2t, tmp, F);
   double n2 = F[0] * F[0];
 #pragma unroll
   for (int i = 1; i < 9; ++i) n2 = n2 + F[i] * F[i];
@@ -434,7 +427,7 @@ __global__ __launch_bounds__(256) void fmat8_kernel(const double* __restrict__ p
     for (int i = 0; i < 3; ++i)
 #pragma unroll
       for (int j = 0; j < 3; ++j) Ft[3 * i + j] = Fh[3 * j + i];
-    mat3(Ft, Fh, G);
+    mat3_ab(Ft, Fh, G);
     smallest_eigvec3(G, v3);
 #pragma unroll
     for (int i = 0; i < 3; ++i) Fv[i] = (Fh[3 * i] * v3[0] + Fh[3 * i + 1] * v3[1]) + Fh[3 * i + 2] * v3[2];

@@ -11,6 +11,7 @@
 // These kernels are HBM-bound: algorithmic traffic = S*P*(8 B track [+1 B detail]) per pass.
 // Compiled with -ffp-contract=off: the boolean outputs are compared bit-for-bit with the oracle.
 #include "common.hpp"
+#include "tri_angle.hpp"
 
 namespace vgg {
 
@@ -97,23 +98,6 @@ __global__ __launch_bounds__(256) void project_kernel(const double* __restrict__
 // inlier pair subtending >= min_tri_angle, widest frame distance first (the reference takes "any").
 constexpr int kFilterThreads = 256;
 
-__device__ __forceinline__ double tri_angle_deg(double r1, double r2, double b) {
-  // law of cosines, min(theta, pi - theta) in degrees -- triangulation_helpers.py:568-586
-  double den = 2.0 * sqrt(r1 * r2);
-  double nom = r1 + r2 - b;
-  if (den <= 1e-12) { nom = 1.0; den = 1.0; }
-  double c = nom / den;
-  c = fmin(fmax(c, -1.0), 1.0);
-  double th = fabs(acos(c));
-  th = fmin(th, 3.141592653589793 - th);
-  return th * (180.0 / 3.141592653589793);
-}
-
-__device__ __forceinline__ double sq_of_norm3(double a, double b, double c) {
-  const double n = sqrt(a * a + b * b + c * c);   // reference: (x).norm(dim=-1) ** 2
-  return n * n;
-}
-
 // kFilterLanes adjacent lanes share one point: lane q projects the frames s = q, q + L, q + 2L, ... (the per-frame
 // projection is a long dependent fp64 chain and one thread per point left 1.5 wavefronts per SIMD at 100k
 // points), the inlier bit-words are OR-combined with shuffles, every lane of the group then holds the whole
@@ -184,9 +168,9 @@ __global__ __launch_bounds__(kFilterThreads) void filter_kernel(
         if (!ib) continue;
         const double* ca = centers + 3 * a;
         const double* cb = centers + 3 * b;
-        const double bsq = sq_of_norm3(ca[0] - cb[0], ca[1] - cb[1], ca[2] - cb[2]);
-        const double r1 = sq_of_norm3(X - ca[0], Y - ca[1], Z - ca[2]);
-        const double r2 = sq_of_norm3(X - cb[0], Y - cb[1], Z - cb[2]);
+        const double bsq = sqnorm3(ca[0] - cb[0], ca[1] - cb[1], ca[2] - cb[2]);
+        const double r1 = sqnorm3(X - ca[0], Y - ca[1], Z - ca[2]);
+        const double r2 = sqnorm3(X - cb[0], Y - cb[1], Z - cb[2]);
         if (tri_angle_deg(r1, r2, bsq) >= min_tri_angle) { tri_any = true; break; }
       }
     }

@@ -17,6 +17,7 @@
 // is compiled with contraction, are restated here, not shared: that file's results stay what they were.
 // No atomics, no cross-lane arithmetic: a point's result does not depend on what else is in the launch.
 #include "common.hpp"
+#include "tri_angle.hpp"
 #include "../../include/vggsfm_amd_multiview.h"
 
 namespace vgg {
@@ -73,11 +74,6 @@ __device__ __forceinline__ void mv_smallest_eigvec4(const double* a, double* v) 
   for (int k = 1; k < 4; ++k) if (A[k][k] < bv) { bv = A[k][k]; best = k; }
 #pragma unroll
   for (int k = 0; k < 4; ++k) v[k] = (best == 0) ? V[k][0] : (best == 1) ? V[k][1] : (best == 2) ? V[k][2] : V[k][3];
-}
-
-__device__ __forceinline__ double mv_sqnorm3(double a, double b, double c) {
-  const double n = sqrt(a * a + b * b + c * c);      // the reference squares a norm: (x).norm(dim=-1) ** 2
-  return n * n;
 }
 
 // triangulation_helpers.py:503-519: law of cosines on squared lengths, min(theta, pi - theta), degrees
@@ -196,11 +192,11 @@ __global__ __launch_bounds__(64) void mv_max_angle_kernel(const double* __restri
   if (FLAG_ONLY ? !__all(found || !live) : __any(live)) {
     for (int i = 0; i + 1 < S; ++i) {
       const double a0 = c[3 * i], a1 = c[3 * i + 1], a2 = c[3 * i + 2];
-      const double r1 = mv_sqnorm3(X0 - a0, X1 - a1, X2 - a2);
+      const double r1 = sqnorm3(X0 - a0, X1 - a1, X2 - a2);
       for (int j = i + 1; j < S; ++j) {
         const double b0 = c[3 * j], b1 = c[3 * j + 1], b2 = c[3 * j + 2];
-        const double bsq = mv_sqnorm3(a0 - b0, a1 - b1, a2 - b2);
-        const double r2 = mv_sqnorm3(X0 - b0, X1 - b1, X2 - b2);
+        const double bsq = sqnorm3(a0 - b0, a1 - b1, a2 - b2);
+        const double r2 = sqnorm3(X0 - b0, X1 - b1, X2 - b2);
         if (FLAG_ONLY) {
           if (live && !found && mv_angle_deg(r1, r2, bsq, kMvEps) >= thr) found = true;
         } else if (live) {
@@ -230,8 +226,8 @@ __global__ __launch_bounds__(256) void mv_angle_table_kernel(const double* __res
   const double* c = SHARED ? centers : centers + b * (long)S * 3;
   const double X0 = points[3 * b], X1 = points[3 * b + 1], X2 = points[3 * b + 2];
   const double a0 = c[3 * i], a1 = c[3 * i + 1], a2 = c[3 * i + 2], b0 = c[3 * j], b1 = c[3 * j + 1], b2 = c[3 * j + 2];
-  out[idx] = mv_angle_deg(mv_sqnorm3(X0 - a0, X1 - a1, X2 - a2), mv_sqnorm3(X0 - b0, X1 - b1, X2 - b2),
-                          mv_sqnorm3(a0 - b0, a1 - b1, a2 - b2), eps);
+  out[idx] = mv_angle_deg(sqnorm3(X0 - a0, X1 - a1, X2 - a2), sqnorm3(X0 - b0, X1 - b1, X2 - b2),
+                          sqnorm3(a0 - b0, a1 - b1, a2 - b2), eps);
 }
 
 // (K, P) table of given centre pairs: the point index fastest
@@ -243,8 +239,8 @@ __global__ __launch_bounds__(256) void mv_angle_pairs_kernel(const double* __res
   const long k = idx / P, p = idx - k * P;
   const double X0 = points[3 * p], X1 = points[3 * p + 1], X2 = points[3 * p + 2];
   const double a0 = c1[3 * k], a1 = c1[3 * k + 1], a2 = c1[3 * k + 2], b0 = c2[3 * k], b1 = c2[3 * k + 1], b2 = c2[3 * k + 2];
-  out[idx] = mv_angle_deg(mv_sqnorm3(X0 - a0, X1 - a1, X2 - a2), mv_sqnorm3(X0 - b0, X1 - b1, X2 - b2),
-                          mv_sqnorm3(a0 - b0, a1 - b1, a2 - b2), eps);
+  out[idx] = mv_angle_deg(sqnorm3(X0 - a0, X1 - a1, X2 - a2), sqnorm3(X0 - b0, X1 - b1, X2 - b2),
+                          sqnorm3(a0 - b0, a1 - b1, a2 - b2), eps);
 }
 
 // calculate_normalized_angular_error_batched: out (P,B,N), the observation index fastest

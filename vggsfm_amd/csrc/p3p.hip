@@ -22,6 +22,7 @@
 //                          (points read once per wavefront, coalesced; counts / residual sums by wave reduction)
 //   p3p_select_kernel      one workgroup per frame: arg-best over the 4H scores, then the inlier mask of the winner
 #include "common.hpp"
+#include "support.hpp"
 #include "../../include/vggsfm_amd.h"
 
 namespace vgg {
@@ -237,18 +238,6 @@ __global__ __launch_bounds__(128) void p3p_hypotheses_kernel(const double* __res
   }
 }
 
-__device__ inline bool point_error(const double* __restrict__ P, double X0, double X1, double X2, double u, double w, double thr_sq,
-                                   double& e) {
-  const double px = ((P[0] * X0 + P[1] * X1) + P[2] * X2) + P[3];
-  const double py = ((P[4] * X0 + P[5] * X1) + P[6] * X2) + P[7];
-  const double pz = ((P[8] * X0 + P[9] * X1) + P[10] * X2) + P[11];
-  const bool front = pz > 1e-12;
-  const double zs = front ? pz : 1.0;
-  const double ex = px / zs - u, ey = py / zs - w;
-  e = ex * ex + ey * ey;
-  return front && e <= thr_sq;
-}
-
 // one wavefront per (frame, sample); counts [F][4H] (-1 for an invalid pose), sums [F][4H]
 __global__ __launch_bounds__(256) void p3p_score_kernel(const double* __restrict__ x, const double* __restrict__ X,
                                                        const uint8_t* __restrict__ mask, int F, int N, int H,
@@ -293,13 +282,6 @@ __global__ __launch_bounds__(256) void p3p_score_kernel(const double* __restrict
   }
 }
 
-// better support: more inliers; then the smaller residual sum; then the lower index
-__device__ inline bool better(int ca, double sa, int ia, int cb, double sb, int ib) {
-  if (ca != cb) return ca > cb;
-  if (sa != sb) return sa < sb;
-  return ia < ib;
-}
-
 __global__ __launch_bounds__(256) void p3p_select_kernel(const double* __restrict__ x, const double* __restrict__ X,
                                                         const uint8_t* __restrict__ mask, int N, int H,
                                                         const double* __restrict__ thr_sq, const double* __restrict__ poses,
@@ -319,14 +301,14 @@ __global__ __launch_bounds__(256) void p3p_select_kernel(const double* __restric
   for (int i = tid; i < M; i += 256) {
     const int ci = cnt[i];
     if (ci < 0) continue;
-    if (bi == 0x7fffffff || better(ci, sm[i], i, bc, bs, bi)) { bc = ci; bs = sm[i]; bi = i; }
+    if (bi == 0x7fffffff || ranks_before(ci, sm[i], i, bc, bs, bi)) { bc = ci; bs = sm[i]; bi = i; }
   }
   sc[tid] = bc; ss[tid] = bs; si[tid] = bi;
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
     if (tid < st) {
       const int oi = si[tid + st];
-      if (oi != 0x7fffffff && (si[tid] == 0x7fffffff || better(sc[tid + st], ss[tid + st], oi, sc[tid], ss[tid], si[tid]))) {
+      if (oi != 0x7fffffff && (si[tid] == 0x7fffffff || ranks_before(sc[tid + st], ss[tid + st], oi, sc[tid], ss[tid], si[tid]))) {
         sc[tid] = sc[tid + st]; ss[tid] = ss[tid + st]; si[tid] = oi;
       }
     }

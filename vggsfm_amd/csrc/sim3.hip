@@ -17,7 +17,8 @@
 #include "common.hpp"
 #include "two_view.hpp"
 #include "kabsch3.hpp"
-#include "vggsfm_amd_sim3.h"
+#include "support.hpp"
+#include "../../include/vggsfm_amd_sim3.h"
 
 namespace vgg {
 
@@ -381,13 +382,6 @@ __global__ __launch_bounds__(256) void sim3_score_reduce_kernel(const uint8_t* _
 }
 
 // ---------------------------------------------------------------------------------------------------------- ransac
-// ranks (count, sum, index): more inliers, then the smaller residual sum, then the lower index: a total order
-__device__ __forceinline__ bool ranks_before(int c1, double s1, int i1, int c2, double s2, int i2) {
-  if (c1 != c2) return c1 > c2;
-  if (s1 != s2) return s1 < s2;
-  return i1 < i2;
-}
-
 __global__ __launch_bounds__(256) void sim3_select_kernel(int H, const double* __restrict__ hyp, const int32_t* __restrict__ counts,
                                                           const double* __restrict__ sums, double* __restrict__ out_T,
                                                           int32_t* __restrict__ out_num, double* __restrict__ out_sum,

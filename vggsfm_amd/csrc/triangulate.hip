@@ -23,10 +23,10 @@
 // launches with 2*pi+1e-6 (true whenever any hypothesis of the chunk has no inlier) and re-launches with
 // the measured maximum in the pathological case that it is not.
 #include "common.hpp"
+#include "tri_angle.hpp"
 
 namespace vgg {
 
-constexpr double kPi = 3.141592653589793;
 #ifndef VGG_TRI_ABLATE
 #define VGG_TRI_ABLATE 0     // profiling builds only: 1 = no RANSAC error loop, 2 = no LO rounds, 3 = neither
 #endif
@@ -219,23 +219,6 @@ __device__ __forceinline__ double acos_near_one(double c) {
 #endif
 }
 
-__device__ __forceinline__ double tri_angle_deg2(double r1, double r2, double b) {
-  // triangulation_helpers.py:503-519: law of cosines on (norm)^2 values, min(theta, pi - theta), degrees
-  double den = 2.0 * sqrt(r1 * r2);
-  double nom = r1 + r2 - b;
-  if (den <= 1e-12) { nom = 1.0; den = 1.0; }
-  double c = nom / den;
-  c = fmin(fmax(c, -1.0), 1.0);
-  double th = fabs(acos(c));
-  th = fmin(th, kPi - th);
-  return th * (180.0 / kPi);
-}
-
-__device__ __forceinline__ double sqnorm3(double a, double b, double c) {
-  const double n = sqrt(a * a + b * b + c * c);
-  return n * n;
-}
-
 // DLT matrix T^T T of one view, T = P - r (r^T P) for the unit ray r (3x4 rows of the projection matrix P)
 __device__ __forceinline__ void view_dlt_matrix_r(const double* __restrict__ P, double r0, double r1, double r2,
                                                   Sym4& m) {
@@ -291,7 +274,7 @@ __device__ __forceinline__ bool any_pair_angle(const double* __restrict__ center
       if (live && !found) {
         const double r1 = sqnorm3(X0 - ca[0], X1 - ca[1], X2 - ca[2]);
         const double r2 = sqnorm3(X0 - cb[0], X1 - cb[1], X2 - cb[2]);
-        if (tri_angle_deg2(r1, r2, bsq) >= thr) found = true;
+        if (tri_angle_deg(r1, r2, bsq) >= thr) found = true;
       }
       if (__all(found || !live)) return found;
     }
@@ -619,7 +602,7 @@ __global__ __launch_bounds__(64, VGG_TRI_OCC) void triangulate_kernel(   // (rou
       const double bsq = sqnorm3(c1[0] - c2[0], c1[1] - c2[1], c1[2] - c2[2]);
       const double r1 = sqnorm3(X[j][0] - c1[0], X[j][1] - c1[1], X[j][2] - c1[2]);
       const double r2 = sqnorm3(X[j][0] - c2[0], X[j][1] - c2[1], X[j][2] - c2[2]);
-      const bool tri_ok = tri_angle_deg2(r1, r2, bsq) >= min_tri_deg;
+      const bool tri_ok = tri_angle_deg(r1, r2, bsq) >= min_tri_deg;
       inv[j] = (z1 <= 0.0) || (z2 <= 0.0) || !tri_ok;
     }
     // ---- angular errors of the RANSAC hypotheses: wave-uniform view loop, HJ independent chains per lane

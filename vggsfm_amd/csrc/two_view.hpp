@@ -1,5 +1,5 @@
-// Device helpers shared by the two-view estimators (fundamental.hip, essential.hip): the squared Sampson distance, the
-// Jacobi rotation and the fixed-order block reduction.  Compiled without floating-point contraction in both files.
+// Device helpers shared by the two-view estimators (fundamental.hip, essential.hip): the 3x3 product, the squared Sampson
+// distance, the Jacobi rotation and the fixed-order block reduction.  Compiled without floating-point contraction in both files.
 #pragma once
 #include "common.hpp"
 
@@ -14,6 +14,14 @@ __device__ inline void jacobi_cs(double app, double aqq, double apq, double& c, 
   const double cc = 1.0 / sqrt(1.0 + t * t);
   c = rot ? cc : 1.0;
   s = rot ? t * cc : 0.0;
+}
+
+// C = A B (3x3 row-major), terms added left to right
+__device__ __forceinline__ void mat3_ab(const double* A, const double* B, double* C) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
 }
 
 // squared Sampson distance of (u1,v1) <-> (u2,v2) under p2^T F p1 = 0
