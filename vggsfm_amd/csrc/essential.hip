@@ -6,7 +6,7 @@
 //   emat5_kernel        a group of 16 lanes per (pair, 5-point sample), four samples per wavefront
 //   emat_gram_kernel    one workgroup per (pair, selected hypothesis) or per point set: X^T X over the inliers (recomputed
 //                       on the fly) or over all weighted rows, fixed-order reductions, then the first wavefront solves
-//   emat_score_kernel   fmat_score_kernel with one threshold per pair
+//   two_view_score_kernel  (two_view.hpp, shared with fundamental.hip) with one threshold per pair
 // Both solvers end in five_point_from_gram(): the 16 lanes of a group hold the 9x9 matrix X^T X, one row per lane.
 //   1  cyclic Jacobi (lane = row); the eigenvectors of the four smallest eigenvalues span E = x N0 + y N1 + z N2 + N3
 //   2  lane r < 9 expands entry r of 2 E E^T E - tr(E E^T) E, lane 9 expands det E: ten cubics in (x, y, z), 20 monomials
@@ -23,7 +23,6 @@
 namespace vgg {
 
 constexpr int kGroup = 16;           // lanes per 5-point problem
-constexpr int kSweepsE = 10;         // Jacobi sweeps of the 9x9 matrix (kSweeps9 of fundamental.hip)
 constexpr int kSturmSteps = 64;      // bisections on the sign-variation count
 constexpr int kNewtonSteps = 3;
 constexpr int kPolishSteps = 4;      // Gauss-Newton steps on the constraints
@@ -191,7 +190,7 @@ __device__ __forceinline__ void five_point_from_gram(double* a, int g, double* E
   double v[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j) v[j] = (j == g) ? 1.0 : 0.0;
-  for (int sw = 0; sw < kSweepsE; ++sw) {
+  for (int sw = 0; sw < kSweeps9; ++sw) {
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
 #pragma unroll
@@ -533,17 +532,14 @@ __global__ __launch_bounds__(256) void emat_gram_kernel(const double* __restrict
   bool src_ok = true;
   double thr_sq = 0.0;
   if (kInliers) {
-    const int src = sel[(size_t)blockIdx.y * L + blockIdx.x];
-    src_ok = src >= 0 && src < Ksrc && src_counts[(size_t)blockIdx.y * Ksrc + (src >= 0 && src < Ksrc ? src : 0)] >= 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Es[i] = src_ok ? Esrc[((size_t)blockIdx.y * Ksrc + src) * 9 + i] : 0.0;
+    src_ok = load_selected(Esrc, src_counts, sel, blockIdx.y, blockIdx.x, Ksrc, L, Es);
     thr_sq = thr[blockIdx.y];
   }
   const double* p1 = pts1 + set * N * 2;
   const double* p2 = pts2 + set * N * 2;
-  double acc[46];
+  double acc[45], rows = 0.0;
 #pragma unroll
-  for (int i = 0; i < 46; ++i) acc[i] = 0.0;
+  for (int i = 0; i < 45; ++i) acc[i] = 0.0;
   for (int n = tid; n < N; n += 256) {
     const double x1 = p1[2 * n], y1 = p1[2 * n + 1], x2 = p2[2 * n], y2 = p2[2 * n + 1];
     double m;
@@ -551,33 +547,11 @@ __global__ __launch_bounds__(256) void emat_gram_kernel(const double* __restrict
     else m = weights ? weights[set * N + n] : 1.0;
     double r[9];
     epipolar_row(x1, y1, x2, y2, r);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r[i] = r[i] * m;
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-      for (int j = i; j < 9; ++j) { acc[e] = acc[e] + r[i] * r[j]; ++e; }
-    acc[45] = acc[45] + ((m != 0.0) ? 1.0 : 0.0);
+    gram_add(acc, r, m);
+    rows = rows + ((m != 0.0) ? 1.0 : 0.0);
   }
-  {
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      double vals[9], outs[9];
-#pragma unroll
-      // (row i of the upper triangle in slots i..8; the last pass carries the row count in its free slot 0)
-      for (int j = 0; j < 9; ++j) vals[j] = (j >= i) ? acc[e + (j - i)] : ((i == 8 && j == 0) ? acc[45] : 0.0);
-      block_tree_sum<9>(red, vals, outs);
-      if (tid == 0) {
-#pragma unroll
-        for (int j = 0; j < 9; ++j)
-          if (j >= i) { Ms[i][j] = outs[j]; Ms[j][i] = outs[j]; }
-        if (i == 8) cnt_s = outs[0];
-      }
-      e += 9 - i;
-    }
-  }
+  const double cnt = gram_reduce(red, acc, Ms, rows);      // (the row count rides in the free slot of the last pass)
+  if (tid == 0) cnt_s = cnt;
   __syncthreads();
   if (tid < 64) {            // the four groups of the first wavefront solve the same matrix; the first one stores
     const int g = tid & (kGroup - 1);
@@ -588,58 +562,6 @@ __global__ __launch_bounds__(256) void emat_gram_kernel(const double* __restrict
     bool valid;
     five_point_from_gram(a, g, E, valid);
     if (tid < 10) store_candidate(outE + (slot0 + tid) * 9, out_valid + slot0 + tid, E, valid && cnt_s >= 5.0);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ scoring
-constexpr int kEmatHypPerWave = 4;   // as fmat_score_kernel: the points are read once for four hypotheses
-
-__global__ __launch_bounds__(256) void emat_score_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
-                                                        const double* __restrict__ Eall, const uint8_t* __restrict__ evalid,
-                                                        const double* __restrict__ thr, int B, int N, int K,
-                                                        int32_t* __restrict__ counts, double* __restrict__ rsums) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long k0 = ((long)blockIdx.x * 4 + wave) * kEmatHypPerWave;
-  const int b = blockIdx.y;
-  if (k0 >= K) return;
-  const double thr_sq = thr[b];
-  double F[kEmatHypPerWave][9];
-  bool live[kEmatHypPerWave];
-  bool any = false;
-#pragma unroll
-  for (int h = 0; h < kEmatHypPerWave; ++h) {
-    const long k = k0 + h;
-    live[h] = k < K && evalid[(size_t)b * K + (k < K ? k : 0)];
-    any = any || live[h];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F[h][i] = live[h] ? Eall[((size_t)b * K + k) * 9 + i] : 0.0;
-  }
-  const double* p1 = pts1 + (size_t)b * N * 2;
-  const double* p2 = pts2 + (size_t)b * N * 2;
-  int c[kEmatHypPerWave];
-  double s[kEmatHypPerWave];
-#pragma unroll
-  for (int h = 0; h < kEmatHypPerWave; ++h) { c[h] = 0; s[h] = 0.0; }
-  if (any) {
-    for (int n = lane; n < N; n += 64) {
-      const double u1 = p1[2 * n], v1 = p1[2 * n + 1], u2 = p2[2 * n], v2 = p2[2 * n + 1];
-#pragma unroll
-      for (int h = 0; h < kEmatHypPerWave; ++h) {
-        const double r = sampson_sq(F[h], u1, v1, u2, v2);
-        const bool in = r <= thr_sq;
-        c[h] += in ? 1 : 0;
-        s[h] = s[h] + (in ? r : 0.0);
-      }
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < kEmatHypPerWave; ++h) {
-    const int ch = wave_sum_i(c[h]);
-    const double sh = wave_sum(s[h]);
-    if (lane == 0 && k0 + h < K) {
-      counts[(size_t)b * K + k0 + h] = live[h] ? ch : -1;
-      rsums[(size_t)b * K + k0 + h] = live[h] ? sh : 0.0;
-    }
   }
 }
 
@@ -681,8 +603,9 @@ int vgge_emat_score(const double* points1, const double* points2, const double* 
   if (!points1 || !points2 || !emat || !emat_valid || !max_error_sq || !out_counts || !out_residual_sums)
     return VGG_ERR_INVALID_ARGUMENT;
   if (num_pairs > 65535) return VGG_ERR_UNSUPPORTED;
-  emat_score_kernel<<<dim3(div_up(num_hypotheses, 4 * kEmatHypPerWave), num_pairs), 256, 0, (hipStream_t)stream>>>(
-      points1, points2, emat, emat_valid, max_error_sq, num_pairs, num_points, num_hypotheses, out_counts, out_residual_sums);
+  two_view_score_kernel<kHypPerWave><<<dim3(div_up(num_hypotheses, 4 * kHypPerWave), num_pairs), 256, 0, (hipStream_t)stream>>>(
+      points1, points2, nullptr, emat, emat_valid, max_error_sq, 0.0, num_pairs, num_points, num_hypotheses, out_counts,
+      out_residual_sums);
   VGG_LAUNCH_CHECK();
   return VGG_OK;
 }

@@ -9,8 +9,7 @@
 //
 //   fmat7_kernel        one thread per (pair, 7-point sample): normalise, null space of the 7x9 system by Gauss-Jordan
 //                       with complete pivoting, cubic det(F1 + lambda F2) = 0 by bisection + deflation, <= 3 matrices
-//   fmat_score_kernel   one wavefront per (pair, hypothesis): squared Sampson distance of all N matches in one sweep
-//                       (coalesced, the pair's points stay in L2 for its K hypotheses), inlier count + residual sum
+//   two_view_score_kernel  (two_view.hpp, shared with essential.hip) inlier count + residual sum of every hypothesis
 //   fmat8_kernel        one workgroup per (pair, selected hypothesis): its inliers are recomputed on the fly, three
 //                       sweeps (means, scales, the 45 sums of X^T X) with fixed-order reductions, then one wavefront
 //                       runs cyclic Jacobi on the 9x9 matrix (lane = row), rank 2, denormalise
@@ -23,7 +22,7 @@
 namespace vgg {
 
 constexpr int kBisections = 110;     // BISECTIONS in oracle/fundamental.py
-constexpr int kSweeps9 = 10, kSweeps3 = 8;
+constexpr int kSweeps3 = 8;
 
 // ------------------------------------------------------------------------------------------------ small solvers
 // real roots of c3 x^3 + c2 x^2 + c1 x + c0 (oracle: cubic_real_roots)
@@ -230,57 +229,6 @@ __global__ __launch_bounds__(64) void fmat7_kernel(const double* __restrict__ pt
 }
 
 // ------------------------------------------------------------------------------------------------ residuals
-constexpr int kHypPerWave = 4;   // hypotheses scored per sweep of a wavefront: the points are read once for all of them
-
-__global__ __launch_bounds__(256) void fmat_score_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
-                                                        const uint8_t* __restrict__ vmask, const double* __restrict__ Fall,
-                                                        const uint8_t* __restrict__ fvalid, int B, int N, int K, double thr_sq,
-                                                        int32_t* __restrict__ counts, double* __restrict__ rsums) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int k0 = (blockIdx.x * 4 + wave) * kHypPerWave, b = blockIdx.y;
-  if (k0 >= K) return;
-  double F[kHypPerWave][9];
-  bool live[kHypPerWave];
-  bool any = false;
-#pragma unroll
-  for (int h = 0; h < kHypPerWave; ++h) {
-    const int k = k0 + h;
-    live[h] = k < K && fvalid[(size_t)b * K + (k < K ? k : 0)];
-    any = any || live[h];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F[h][i] = live[h] ? Fall[((size_t)b * K + k) * 9 + i] : 0.0;
-  }
-  const double* p1 = pts1 + (size_t)b * N * 2;
-  const double* p2 = pts2 + (size_t)b * N * 2;
-  const uint8_t* vm = vmask ? vmask + (size_t)b * N : nullptr;
-  int c[kHypPerWave];
-  double s[kHypPerWave];
-#pragma unroll
-  for (int h = 0; h < kHypPerWave; ++h) { c[h] = 0; s[h] = 0.0; }
-  if (any) {
-    for (int n = lane; n < N; n += 64) {
-      const double u1 = p1[2 * n], v1 = p1[2 * n + 1], u2 = p2[2 * n], v2 = p2[2 * n + 1];
-      const bool usable = !vm || vm[n];
-#pragma unroll
-      for (int h = 0; h < kHypPerWave; ++h) {
-        const double r = sampson_sq(F[h], u1, v1, u2, v2);
-        const bool in = r <= thr_sq && usable;
-        c[h] += in ? 1 : 0;
-        s[h] = s[h] + (in ? r : 0.0);
-      }
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < kHypPerWave; ++h) {
-    const int ch = wave_sum_i(c[h]);
-    const double sh = wave_sum(s[h]);
-    if (lane == 0 && k0 + h < K) {
-      counts[(size_t)b * K + k0 + h] = live[h] ? ch : -1;
-      rsums[(size_t)b * K + k0 + h] = live[h] ? sh : 0.0;
-    }
-  }
-}
-
 __global__ __launch_bounds__(256) void fmat_residuals_kernel(const double* __restrict__ pts1, const double* __restrict__ pts2,
                                                             const uint8_t* __restrict__ vmask, const double* __restrict__ Fb,
                                                             int B, int N, double* __restrict__ out) {
@@ -304,11 +252,8 @@ __global__ __launch_bounds__(256) void fmat8_kernel(const double* __restrict__ p
   __shared__ double Ms[9][9];
   __shared__ double fvec[9];
   const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
-  const int src = sel[(size_t)b * L + l];
-  const bool src_ok = src >= 0 && src < Ksrc && src_counts[(size_t)b * Ksrc + (src >= 0 && src < Ksrc ? src : 0)] >= 0;
   double Fs[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) Fs[i] = src_ok ? Fsrc[((size_t)b * Ksrc + src) * 9 + i] : 0.0;
+  const bool src_ok = load_selected(Fsrc, src_counts, sel, b, l, Ksrc, L, Fs);
   const double* p1 = pts1 + (size_t)b * N * 2;
   const double* p2 = pts2 + (size_t)b * N * 2;
   const uint8_t* vm = vmask ? vmask + (size_t)b * N : nullptr;
@@ -350,30 +295,10 @@ __global__ __launch_bounds__(256) void fmat8_kernel(const double* __restrict__ p
     double u1, v1, u2, v2;
     const bool in = inlier(n, u1, v1, u2, v2);
     const double a1 = s1 * u1 + T1[2], b1 = s1 * v1 + T1[5], a2 = s2 * u2 + T2[2], b2 = s2 * v2 + T2[5];
-    const double m = in ? 1.0 : 0.0;
-    const double row[9] = {(a2 * a1) * m, (a2 * b1) * m, a2 * m, (b2 * a1) * m, (b2 * b1) * m, b2 * m, a1 * m, b1 * m, 1.0 * m};
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-      for (int j = i; j < 9; ++j) { acc[e] = acc[e] + row[i] * row[j]; ++e; }
+    const double row[9] = {a2 * a1, a2 * b1, a2, b2 * a1, b2 * b1, b2, a1, b1, 1.0};
+    gram_add(acc, row, in ? 1.0 : 0.0);
   }
-  {
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      double vals[9], outs[9];
-#pragma unroll
-      for (int j = 0; j < 9; ++j) vals[j] = (j >= i) ? acc[e + (j - i)] : 0.0;
-      block_tree_sum<9>(red, vals, outs);
-      if (tid == 0) {
-#pragma unroll
-        for (int j = 0; j < 9; ++j)
-          if (j >= i) { Ms[i][j] = outs[j]; Ms[j][i] = outs[j]; }
-      }
-      e += 9 - i;
-    }
-  }
+  gram_reduce(red, acc, Ms);
   __syncthreads();
   // cyclic Jacobi on the 9x9 matrix by one wavefront: lane = row of A and of V
   if (tid < 64) {
@@ -471,8 +396,9 @@ int vgg_fmat_score(const double* points1, const double* points2, const uint8_t* 
   if (num_pairs == 0) return VGG_OK;
   if (!points1 || !points2 || !fmat || !fmat_valid || !out_counts || !out_residual_sums) return VGG_ERR_INVALID_ARGUMENT;
   if (num_pairs > 65535) return VGG_ERR_UNSUPPORTED;
-  fmat_score_kernel<<<dim3(div_up(num_hypotheses, 4 * kHypPerWave), num_pairs), 256, 0, (hipStream_t)stream>>>(
-      points1, points2, valid_mask, fmat, fmat_valid, num_pairs, num_points, num_hypotheses, max_error_sq, out_counts, out_residual_sums);
+  two_view_score_kernel<kHypPerWave><<<dim3(div_up(num_hypotheses, 4 * kHypPerWave), num_pairs), 256, 0, (hipStream_t)stream>>>(
+      points1, points2, valid_mask, fmat, fmat_valid, nullptr, max_error_sq, num_pairs, num_points, num_hypotheses, out_counts,
+      out_residual_sums);
   VGG_LAUNCH_CHECK();
   return VGG_OK;
 }

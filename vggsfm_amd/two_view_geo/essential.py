@@ -10,9 +10,7 @@ reference scores in float32)."""
 import torch
 
 from .. import _lib
-from .utils import generate_samples
-
-BIG = 1e6
+from .utils import generate_samples, pick_winner, select_best
 
 
 def _score(L, p1, p2, E, valid, thr):
@@ -80,23 +78,12 @@ def estimate_essential(points1, points2, focal_length, principal_point, max_rans
     Ea, va = _five_point(L, p1, p2, smp)
     cnt, rs = _score(L, p1, p2, Ea, va, thr)
     lo = min(int(lo_num), Ea.shape[1])
-    Eall, call, rall = Ea, cnt.long(), rs
+    Eall, call, rall = Ea, cnt, rs
     if lo > 0:                                  # (lo_num = 0: no local optimisation, as in the reference)
-        order = torch.sort(cnt, dim=1, descending=True, stable=True).indices[:, :lo].to(torch.int32).contiguous()
-        El, vl = _refine(L, p1, p2, Ea, cnt, order, thr)
+        El, vl = _refine(L, p1, p2, Ea, cnt, select_best(cnt, lo), thr)
         cl, rl = _score(L, p1, p2, El, vl, thr)
-        Eall, call, rall = torch.cat([Ea, El], 1), torch.cat([cnt, cl], 1).long(), torch.cat([rs, rl], 1)
-    # most inliers, then the smallest mean inlier residual, then the lowest index (two_view_geo/utils.py:63-87)
-    mean = torch.where(call > 0, rall / call.clamp(min=1).double(), torch.full_like(rall, BIG))
-    top = call.max(dim=1, keepdim=True).values
-    best = torch.where(call == top, mean, torch.full_like(mean, float("inf"))).argmin(dim=1)
-    ar = torch.arange(B, device=dev)
-    Eb = Eall[ar, best].contiguous()
-    res = torch.empty((B, N), dtype=torch.float64, device=dev)
-    _lib.check(L.vgg_fmat_residuals(p1, p2, None, Eb, B, N, res, _lib.stream_ptr()), "vgg_fmat_residuals")
-    found = call[ar, best] >= 0
-    mask = (res <= thr[:, None]) & found[:, None]
-    num = torch.where(found, call[ar, best], torch.zeros_like(top[:, 0]))
+        Eall, call, rall = torch.cat([Ea, El], 1), torch.cat([cnt, cl], 1), torch.cat([rs, rl], 1)
+    Eb, num, mask, res = pick_winner(p1, p2, None, Eall, call, rall, thr)
     if return_residuals:
         return Eb.reshape(B, 3, 3), num, mask, res
     return Eb.reshape(B, 3, 3), num, mask

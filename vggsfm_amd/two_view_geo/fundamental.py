@@ -6,9 +6,7 @@ only host-side step between the launches is the stable sort that selects the lo_
 import torch
 
 from .. import _lib
-from .utils import generate_samples
-
-BIG = 1e6
+from .utils import generate_samples, pick_winner, select_best
 
 
 def _score(L, p1, p2, vm, F, fvalid, thr):
@@ -24,7 +22,7 @@ def _eight_point(L, p1, p2, vm, Fsrc, cnt_src, lo, thr):
     B, N = p1.shape[0], p1.shape[1]
     K = Fsrc.shape[1]
     lo = min(int(lo), K)
-    order = torch.sort(cnt_src, dim=1, descending=True, stable=True).indices[:, :lo].to(torch.int32).contiguous()
+    order = select_best(cnt_src, lo)
     F = torch.empty((B, lo, 9), dtype=torch.float64, device=p1.device)
     ok = torch.empty((B, lo), dtype=torch.uint8, device=p1.device)
     _lib.check(L.vgg_fmat_eight_point(p1, p2, vm, Fsrc, cnt_src, order, B, N, K, lo, thr, F, ok, _lib.stream_ptr()),
@@ -73,18 +71,7 @@ def estimate_fundamental(points1, points2, max_ransac_iters=4096, max_error=1, l
             F9, v9 = _eight_point(L, p1, p2, vm, F8, c8, lo_num // 2, thr)
         c9, r9 = _score(L, p1, p2, vm, F9, v9, thr)
         allF.append(F9); allc.append(c9); allr.append(r9)                       # noqa: E702
-    Fall, call, rall = torch.cat(allF, 1), torch.cat(allc, 1).long(), torch.cat(allr, 1)
-    # most inliers, then the smallest mean inlier residual, then the lowest index (two_view_geo/utils.py:63-87)
-    mean = torch.where(call > 0, rall / call.clamp(min=1).double(), torch.full_like(rall, BIG))
-    top = call.max(dim=1, keepdim=True).values
-    best = torch.where(call == top, mean, torch.full_like(mean, float("inf"))).argmin(dim=1)
-    ar = torch.arange(B, device=dev)
-    Fb = Fall[ar, best].contiguous()
-    res = torch.empty((B, N), dtype=torch.float64, device=dev)
-    _lib.check(L.vgg_fmat_residuals(p1, p2, vm, Fb, B, N, res, _lib.stream_ptr()), "vgg_fmat_residuals")
-    found = call[ar, best] >= 0
-    mask = (res <= thr) & found[:, None]
-    num = torch.where(found, call[ar, best], torch.zeros_like(top[:, 0]))
+    Fb, num, mask, res = pick_winner(p1, p2, vm, torch.cat(allF, 1), torch.cat(allc, 1), torch.cat(allr, 1), thr)
     F33 = Fb[:, 8:9]
     Fn = torch.where(F33.abs() > 1e-8, Fb / torch.where(F33.abs() > 1e-8, F33, torch.ones_like(F33)), Fb).reshape(B, 3, 3)
     if return_residuals:

@@ -1,10 +1,13 @@
 """Helpers of the two-view stage under the reference's names (vggsfm/two_view_geo/utils.py): the sample generator, the
-Sampson distance and the inlier test on the device (``vgg_fmat_residuals``), the hypothesis score, and the re-exports
-of the helpers `estimate_preliminary_cameras` uses."""
+Sampson distance and the inlier test on the device (``vgg_fmat_residuals``), the hypothesis score, the tail that
+`estimate_fundamental` and `estimate_essential` share (`select_best`, `pick_winner`), and the re-exports of the helpers
+`estimate_preliminary_cameras` uses."""
 import numpy as np
 import torch
 
 from .. import _lib
+
+BIG = 1e6       # mean inlier residual of a hypothesis without inliers
 
 
 def generate_samples(N, target_num, sample_num, expand_ratio=2):
@@ -15,6 +18,31 @@ def generate_samples(N, target_num, sample_num, expand_ratio=2):
     srt = np.sort(draw, axis=1)
     distinct = (srt[:, 1:] != srt[:, :-1]).all(axis=1)
     return draw[distinct][:target_num]
+
+
+def select_best(counts, lo):
+    """The `lo` hypotheses with the most inliers of every pair, ties to the lower index: counts (B,K) -> (B,lo) int32."""
+    return torch.sort(counts, dim=1, descending=True, stable=True).indices[:, :lo].to(torch.int32).contiguous()
+
+
+def pick_winner(p1, p2, vm, models, counts, rsums, thr):
+    """The last stage of both RANSAC flows.  models (B,K,9), counts (B,K) (-1: dead hypothesis) and residual sums (B,K) of
+    all rounds; vm (B,N) uint8 or None; thr the squared threshold, a float or (B,).  The winner has the most inliers, then
+    the smallest mean inlier residual, then the lowest index (two_view_geo/utils.py:63-87); one `vgg_fmat_residuals` launch
+    gives its residuals.  Returns (model (B,9), inlier_num (B,), inlier_mask (B,N), residuals (B,N))."""
+    B, N = p1.shape[0], p1.shape[1]
+    call = counts.long()
+    mean = torch.where(call > 0, rsums / call.clamp(min=1).double(), torch.full_like(rsums, BIG))
+    top = call.max(dim=1, keepdim=True).values
+    best = torch.where(call == top, mean, torch.full_like(mean, float("inf"))).argmin(dim=1)
+    ar = torch.arange(B, device=p1.device)
+    Mb = models[ar, best].contiguous()
+    res = torch.empty((B, N), dtype=torch.float64, device=p1.device)
+    _lib.check(_lib.lib().vgg_fmat_residuals(p1, p2, vm, Mb, B, N, res, _lib.stream_ptr()), "vgg_fmat_residuals")
+    found = call[ar, best] >= 0
+    mask = (res <= (thr[:, None] if isinstance(thr, torch.Tensor) else thr)) & found[:, None]
+    num = torch.where(found, call[ar, best], torch.zeros_like(top[:, 0]))
+    return Mb, num, mask, res
 
 
 def calculate_residual_indicator(residuals, max_residual, debug=False, check=False, nanvalue=1e6):
