@@ -12,6 +12,7 @@ and the winner selection agree (2e-8 on the matrices in float64; the reference's
 the 7-point stage -- null-space pencil, cubic coefficients, scaling, de-normalisation -- run in the reference's float32
 with kornia's normalize_points restated and its solve_cubic replaced by numpy.roots (median 1e-4 on unit-norm matrices).
 NOT pinned: kornia's own cubic solver and the RNG.
+The 7-point solver and the 8-point fit are pinned against independent long-double solvers (tests/fundamental_cases.py).
 What is restated is the algorithm as the reference states
 it, in float64:
 
@@ -25,7 +26,7 @@ it, in float64:
 
 with these documented differences in HOW (never in what is selected): the null space of the 7x9 system comes from
 Gauss-Jordan elimination with complete pivoting instead of an SVD (any basis spans the same pencil), the pencil is
-parametrised F = F1 + lambda F2, the cubic is solved by bisection + deflation (no transcendental functions, so that this
+parametrised F = F1 + lambda F2 (plus its solution at lambda = infinity when det F2 ~ 0), the cubic is solved by bisection + deflation (no transcendental functions, so that this
 file and csrc/fundamental.hip agree bit for bit), symmetric eigenproblems (9x9 normal matrix, 3x3 rank-2 projection)
 use cyclic Jacobi with a fixed number of sweeps, and every sum runs in the fixed order of the kernels' reductions.
 Only ``tests/`` may import this module.
@@ -250,6 +251,17 @@ def seven_point(p1, p2):
         c1 = 0.5 * (dp - dm) - c3
         lam, okr = cubic_real_roots(c3, c2, c1, c0)            # (M,3)
         Fh = F1[:, None] + lam[..., None, None] * F2[:, None]
+        # the chart F1 + lambda F2 has no place for the pencil's solution at lambda = infinity: when the cubic loses its
+        # leading term (det F2 ~ 0, e.g. a pure sideways translation, where Gauss-Jordan returns the true matrix as a
+        # basis vector) that solution is mu F1 + F2 with mu = 1 / lambda ~ -c3 / c2, and it takes the slot the
+        # quadratic leaves free
+        mx = np.abs(c3) + np.abs(c2) + np.abs(c1) + np.abs(c0)
+        at_inf = ~(np.abs(c3) > 1e-12 * mx)
+        is_quad = at_inf & (np.abs(c2) > 1e-12 * mx)
+        mu = np.where(is_quad, -c3 / np.where(is_quad, c2, 1.0), 0.0)
+        Fh[:, 2] = np.where(at_inf[:, None, None], mu[:, None, None] * F1 + F2, Fh[:, 2])
+        okr = okr.copy()
+        okr[:, 2] = np.where(at_inf, True, okr[:, 2])
         F = _denormalize(Fh, T1[:, None], T2[:, None])
         F, n = _unit(F)
         valid = okr & ok[:, None] & np.isfinite(F).all((-1, -2)) & (n > 0.0)
@@ -346,12 +358,14 @@ def estimate_fundamental_pair(x1, x2, vmask, samples, max_error, lo_num=300, sec
     F7, v7 = seven_point(x1[samples], x2[samples])
     Fa, va = F7.reshape(-1, 3, 3), v7.reshape(-1)
     cnt, rs, inl = score(Fa, va, x1, x2, vmask, thr)
+    allF, allc, allr, alli = [Fa], [cnt], [rs], [inl]
     lo = min(lo_num, len(cnt))
-    top = _order(cnt)[:lo]
-    F8, v8 = eight_point(x1, x2, inl[top] & (cnt[top] >= 0)[:, None])
-    c8, r8, i8 = score(F8, v8, x1, x2, vmask, thr)
-    allF, allc, allr, alli = [Fa, F8], [cnt, c8], [rs, r8], [inl, i8]
-    if second_refine:
+    if lo > 0:                                                 # lo_num = 0: no local optimisation
+        top = _order(cnt)[:lo]
+        F8, v8 = eight_point(x1, x2, inl[top] & (cnt[top] >= 0)[:, None])
+        c8, r8, i8 = score(F8, v8, x1, x2, vmask, thr)
+        allF.append(F8); allc.append(c8); allr.append(r8); alli.append(i8)      # noqa: E702
+    if second_refine and lo > 0 and lo_num // 2 > 0:           # lo_num = 1: no second round
         lo2 = min(lo_num // 2, len(c8))
         # fundamental.py:126-152: the second round ranks and refits on residuals_lo BEFORE valid_mask is applied
         c8u, _, i8u = score(F8, v8, x1, x2, np.ones_like(vmask), thr)

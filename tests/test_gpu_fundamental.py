@@ -1,7 +1,8 @@
 """GPU: the two-view kernels (vgg_fmat_* through the C-ABI) against oracle/fundamental.py on the SAME samples -- the
 two mirror each other operation by operation (float64, no FMA contraction, fixed-order sums), so hypotheses, counts,
 winners and inlier masks must be identical -- plus the behaviour of ``estimate_preliminary_cameras`` on a synthetic
-sequence.  Parity with the reference's float32 / kornia implementation is unpinned (oracle/fundamental.py header)."""
+sequence.  Parity with the reference's float32 / kornia implementation is unpinned (oracle/fundamental.py header).
+The 7-point solver is pinned against an independent long-double solver in tests/test_gpu_fundamental_regimes.py."""
 
 import numpy as np
 import pytest

@@ -8,7 +8,8 @@
 // (-ffp-contract=off), no transcendental functions, every sum in a fixed order.
 //
 //   fmat7_kernel        one thread per (pair, 7-point sample): normalise, null space of the 7x9 system by Gauss-Jordan
-//                       with complete pivoting, cubic det(F1 + lambda F2) = 0 by bisection + deflation, <= 3 matrices
+//                       with complete pivoting, cubic det(F1 + lambda F2) = 0 by bisection + deflation (and the root at
+//                       lambda = infinity when det F2 ~ 0), <= 3 matrices
 //   two_view_score_kernel  (two_view.hpp, shared with essential.hip) inlier count + residual sum of every hypothesis
 //   fmat8_kernel        one workgroup per (pair, selected hypothesis): its inliers are recomputed on the fly, three
 //                       sweeps (means, scales, the 45 sums of X^T X) with fixed-order reductions, then one wavefront
@@ -212,14 +213,20 @@ __global__ __launch_bounds__(64) void fmat7_kernel(const double* __restrict__ pt
   double lam[3];
   bool okr[3];
   cubic_real_roots(c3, c2, c1, c0, lam, okr);
+  // the pencil's solution at lambda = infinity (det F2 ~ 0: the cubic loses its leading term and slot 2 is free):
+  // mu F1 + F2 with mu = 1 / lambda ~ -c3 / c2 (oracle: seven_point)
+  const double cmx = fabs(c3) + fabs(c2) + fabs(c1) + fabs(c0);
+  const bool at_inf = !(fabs(c3) > 1e-12 * cmx);
+  const bool inf_quad = at_inf && fabs(c2) > 1e-12 * cmx;
+  const double mu = inf_quad ? -c3 / c2 : 0.0;
   double* out = outF + ((size_t)b * H + h) * 27;
   uint8_t* vout = out_valid + ((size_t)b * H + h) * 3;
   for (int s = 0; s < 3; ++s) {
     double Fh[9], F[9];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) Fh[j] = F1[j] + lam[s] * F2[j];
+    for (int j = 0; j < 9; ++j) Fh[j] = (s == 2 && at_inf) ? mu * F1[j] + F2[j] : F1[j] + lam[s] * F2[j];
     const double n = denormalize_unit(Fh, T1, T2, F);
-    bool v = okr[s] && ok && n > 0.0;
+    bool v = (okr[s] || (s == 2 && at_inf)) && ok && n > 0.0;
 #pragma unroll
     for (int j = 0; j < 9; ++j) v = v && isfinite(F[j]);
 #pragma unroll

@@ -38,6 +38,8 @@ def estimate_fundamental(points1, points2, max_ransac_iters=4096, max_error=1, l
     materialise the (B,K,N) residual tensor it was there to avoid)."""
     if not squared:
         raise NotImplementedError("only squared Sampson thresholds (the reference's default) are implemented")
+    if int(lo_num) < 0:
+        raise ValueError(f"lo_num must be >= 0, got {lo_num}")
     _lib.require_gpu(points1, points2, valid_mask)
     L = _lib.lib()
     dev = points1.device
@@ -57,18 +59,21 @@ def estimate_fundamental(points1, points2, max_ransac_iters=4096, max_error=1, l
     _lib.check(L.vgg_fmat_seven_point(p1, p2, smp, B, N, H, F7, v7, _lib.stream_ptr()), "vgg_fmat_seven_point")
     Fa, va = F7.reshape(B, 3 * H, 9), v7.reshape(B, 3 * H)
     cnt, rs = _score(L, p1, p2, vm, Fa, va, thr)
-    F8, v8 = _eight_point(L, p1, p2, vm, Fa, cnt, lo_num, thr)
-    c8, r8 = _score(L, p1, p2, vm, F8, v8, thr)
-    allF, allc, allr = [Fa, F8], [cnt, c8], [rs, r8]
-    if second_refine:
+    allF, allc, allr = [Fa], [cnt], [rs]
+    lo, lo2 = int(lo_num), int(lo_num) // 2
+    if lo > 0:                                  # (lo_num = 0: no local optimisation, the winner is a 7-point candidate)
+        F8, v8 = _eight_point(L, p1, p2, vm, Fa, cnt, lo, thr)
+        c8, r8 = _score(L, p1, p2, vm, F8, v8, thr)
+        allF.append(F8); allc.append(c8); allr.append(r8)                       # noqa: E702
+    if second_refine and lo2 > 0:               # (lo_num = 1: one refit and no second round)
         # the reference ranks and refits the second round on residuals_lo BEFORE its valid mask is applied
         # (fundamental.py:126-152): invalid matches take part there, and only there
         if vm is not None and not bool(vm.all()):
             ones = torch.ones_like(vm)
             c8u, _ = _score(L, p1, p2, ones, F8, v8, thr)
-            F9, v9 = _eight_point(L, p1, p2, ones, F8, c8u, lo_num // 2, thr)
+            F9, v9 = _eight_point(L, p1, p2, ones, F8, c8u, lo2, thr)
         else:
-            F9, v9 = _eight_point(L, p1, p2, vm, F8, c8, lo_num // 2, thr)
+            F9, v9 = _eight_point(L, p1, p2, vm, F8, c8, lo2, thr)
         c9, r9 = _score(L, p1, p2, vm, F9, v9, thr)
         allF.append(F9); allc.append(c9); allr.append(r9)                       # noqa: E702
     Fb, num, mask, res = pick_winner(p1, p2, vm, torch.cat(allF, 1), torch.cat(allc, 1), torch.cat(allr, 1), thr)
