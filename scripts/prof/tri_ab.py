@@ -1,5 +1,5 @@
-"""triangulate_tracks timing at configs[1] / configs[2] for whatever library VGGSFM_AMD_LIB selects (variant builds of
-triangulate.hip: -DVGG_TRI_EIG=0 / -DVGG_TRI_FAST_ERR=0 / -DVGG_TRI_OCC=n / -DVGG_TRI_STATS); the scene is cached in /tmp
+"""triangulate_tracks timing at configs[1] / configs[2] for whatever library VGGSFM_AMD_LIB selects (the library of another
+commit, or a variant build of triangulate.hip: -DVGG_TRI_ABLATE=n / -DVGG_TRI_OCC=n / -DVGG_TRI_STATS); the scene is cached in /tmp
 so that several variants in one GPU call do not each pay for its generation.  Prints one JSON line per configuration."""
 import ctypes
 import json

@@ -52,6 +52,25 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 }
 __device__ __forceinline__ double wave_bcast(double v, int src) { return __shfl(v, src, 64); }
 
+// fixed-order reduction of Q quantities over the 256 threads: halving tree (t, t + 128), (t, t + 64), ...
+template <int Q>
+__device__ inline void block_tree_sum(double (*red)[256], const double* val, double* out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) red[q][tid] = val[q];
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) red[q][tid] = red[q][tid] + red[q][tid + st];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) out[q] = red[q][0];
+  __syncthreads();
+}
+
 template <typename T>
 __device__ __forceinline__ double load_f64(const T* p) { return (double)(*p); }
 

@@ -16,7 +16,7 @@
 //   5  err_2d and err_3d of the candidates in one sweep (block tree of 8); the winner is the first minimum of err_2d
 // A masked-out point is skipped: nothing read from its slots enters a sum.
 #include "common.hpp"
-#include "two_view.hpp"
+#include "jacobi.hpp"
 #include "kabsch3.hpp"
 #include "support.hpp"
 #include "../../include/vggsfm_amd_pnp.h"
@@ -226,6 +226,8 @@ __device__ __forceinline__ bool epnp_block(EpnpShared& sh, const double* x, cons
     double a[12], v[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) { a[j] = sh.G[rg][j]; v[j] = (j == g) ? 1.0 : 0.0; }
+    // (jacobi_rows<12, 16, kSweeps12> of jacobi.hpp is this loop.  It is written out here because through the helper
+    //  epnp_solve_kernel came out 290 instructions longer and 1.1 % slower: DESIGN.md section 23)
     for (int sw = 0; sw < kSweeps12; ++sw) {
 #pragma unroll
       for (int p = 0; p < 11; ++p) {
@@ -249,18 +251,8 @@ __device__ __forceinline__ bool epnp_block(EpnpShared& sh, const double* x, cons
         }
       }
     }
-    double ev[12];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) ev[j] = shfl16(a[j], j);
-    double nb[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      int rank = 0;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) rank += (ev[i] < ev[j] || (ev[i] == ev[j] && i < j)) ? 1 : 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) nb[k] = (rank == k) ? v[j] : nb[k];
-    }
+    double nb[4];
+    smallest_by_rank<12, 4, 16, false>(a, v, nb);
     // the sign of an eigenvector is the solver's choice, and case 3 depends on it (it divides by clamp(coord_0, 1e-9), and
     // coord_0 carries the sign of B12): the component of largest magnitude, the first such, is made positive
 #pragma unroll

@@ -17,6 +17,7 @@
 //   7  a fixed number of Gauss-Newton steps on the ten constraints polish the coefficients; E is scaled to unit Frobenius
 //      norm and transposed
 #include "common.hpp"
+#include "jacobi.hpp"
 #include "two_view.hpp"
 #include "../../include/vggsfm_amd_essential.h"
 
@@ -190,42 +191,10 @@ __device__ __forceinline__ void five_point_from_gram(double* a, int g, double* E
   double v[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j) v[j] = (j == g) ? 1.0 : 0.0;
-  for (int sw = 0; sw < kSweeps9; ++sw) {
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 9; ++q) {
-        const double app = gshfl(a[p], p), aqq = gshfl(a[q], q), apq = gshfl(a[q], p);
-        double c, s;
-        jacobi_cs(app, aqq, apq, c, s);
-        { const double cp = a[p], cq = a[q]; a[p] = c * cp - s * cq; a[q] = s * cp + c * cq; }      // columns p, q
-        double rp[9], rq[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { rp[j] = gshfl(a[j], p); rq[j] = gshfl(a[j], q); }
-        if (g == p) {
-#pragma unroll
-          for (int j = 0; j < 9; ++j) a[j] = c * rp[j] - s * rq[j];
-        } else if (g == q) {
-#pragma unroll
-          for (int j = 0; j < 9; ++j) a[j] = s * rp[j] + c * rq[j];
-        }
-        { const double vp = v[p], vq = v[q]; v[p] = c * vp - s * vq; v[q] = s * vp + c * vq; }      // V columns
-      }
-    }
-  }
-  // the four smallest eigenvalues (ties: lower index first); nb[k] = component g of basis vector k, N3 the smallest
-  double ev[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) ev[j] = gshfl(a[j], j);
-  double nb[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    int rank = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rank += (ev[i] < ev[j] || (ev[i] == ev[j] && i < j)) ? 1 : 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) nb[k] = (rank == 3 - k) ? v[j] : nb[k];
-  }
+  jacobi_rows<9, kGroup, kSweeps9>(a, v, g);
+  // the four smallest eigenvalues; nb[k] = component g of basis vector k, N3 the smallest
+  double nb[4];
+  smallest_by_rank<9, 4, kGroup, true>(a, v, nb);
   // 2 -- the ten cubic constraints, one per lane
   double row[20];
 #pragma unroll

@@ -17,13 +17,14 @@
 //   fmat_residuals_kernel  residuals of the winner (B x N)
 // Selection of the lo_num best hypotheses (a stable sort of K integers per pair) is left to the caller.
 #include "common.hpp"
+#include "jacobi.hpp"
 #include "two_view.hpp"
 #include "../../include/vggsfm_amd.h"
 
 namespace vgg {
 
 constexpr int kBisections = 110;     // BISECTIONS in oracle/fundamental.py
-constexpr int kSweeps3 = 8;
+constexpr int kSweepsRank2 = 8;      // Jacobi sweeps of the 3x3 matrix F^T F (the rank-2 projection of fmat8_kernel)
 
 // ------------------------------------------------------------------------------------------------ small solvers
 // real roots of c3 x^3 + c2 x^2 + c1 x + c0 (oracle: cubic_real_roots)
@@ -101,22 +102,7 @@ __device__ inline void smallest_eigvec3(const double* G, double* v3) {
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) { A[i][j] = G[3 * i + j]; V[i][j] = (i == j) ? 1.0 : 0.0; }
-  for (int sw = 0; sw < kSweeps3; ++sw) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        double c, s;
-        jacobi_cs(A[p][p], A[q][q], A[p][q], c, s);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { const double cp = A[i][p], cq = A[i][q]; A[i][p] = c * cp - s * cq; A[i][q] = s * cp + c * cq; }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { const double rp = A[p][j], rq = A[q][j]; A[p][j] = c * rp - s * rq; A[q][j] = s * rp + c * rq; }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { const double vp = V[i][p], vq = V[i][q]; V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq; }
-      }
-    }
-  }
+  jacobi_sym3<kSweepsRank2, true>(A, V);
   int jm = 0;
   double dm = A[0][0];
   if (A[1][1] < dm) { dm = A[1][1]; jm = 1; }
@@ -314,29 +300,7 @@ __global__ __launch_bounds__(256) void fmat8_kernel(const double* __restrict__ p
     double a[9], v[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) { a[j] = Ms[rowi][j]; v[j] = (j == rowi) ? 1.0 : 0.0; }
-    for (int sw = 0; sw < kSweeps9; ++sw) {
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-#pragma unroll
-        for (int q = p + 1; q < 9; ++q) {
-          const double app = __shfl(a[p], p, 64), aqq = __shfl(a[q], q, 64), apq = __shfl(a[q], p, 64);
-          double c, s;
-          jacobi_cs(app, aqq, apq, c, s);
-          { const double cp = a[p], cq = a[q]; a[p] = c * cp - s * cq; a[q] = s * cp + c * cq; }      // columns p, q
-          double rp[9], rq[9];
-#pragma unroll
-          for (int j = 0; j < 9; ++j) { rp[j] = __shfl(a[j], p, 64); rq[j] = __shfl(a[j], q, 64); }
-          if (lane == p) {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) a[j] = c * rp[j] - s * rq[j];
-          } else if (lane == q) {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) a[j] = s * rp[j] + c * rq[j];
-          }
-          { const double vp = v[p], vq = v[q]; v[p] = c * vp - s * vq; v[q] = s * vp + c * vq; }      // V columns
-        }
-      }
-    }
+    jacobi_rows<9, 64, kSweeps9>(a, v, lane);
     // first minimum of the diagonal -> its eigenvector (column of V)
     double dmin = __shfl(a[0], 0, 64);
     int jm = 0;

@@ -192,8 +192,7 @@ __global__ __launch_bounds__(kFilterThreads) void filter_kernel(
 __global__ void centers_kernel(const double* __restrict__ ext, int S, double* __restrict__ centers) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
-  const double* E = ext + 12 * s;
-  for (int j = 0; j < 3; ++j) centers[3 * s + j] = -(E[0 + j] * E[3] + E[4 + j] * E[7] + E[8 + j] * E[11]);
+  camera_centre(ext + 12 * s, centers + 3 * s);
 }
 
 // ------------------------------------------------------------------ cam_from_img

@@ -2,7 +2,7 @@
 // floating-point contraction in both files.
 #pragma once
 #include "common.hpp"
-#include "two_view.hpp"
+#include "jacobi.hpp"
 
 namespace vgg {
 

@@ -13,10 +13,12 @@
 // loads); with per-group cameras every lane reads its own.  The angle pass is a second kernel: per point the maximum over
 // the S(S-1)/2 unordered pairs (the expression is symmetric in the two cameras bit for bit, and a diagonal pair gives
 // exactly 0: sqrt(r*r) == r), or the (B,S*S) table for the namesakes.
-// This file is compiled with -ffp-contract=off (the reference's unfused arithmetic); the helpers of triangulate.hip, which
-// is compiled with contraction, are restated here, not shared: that file's results stay what they were.
+// This file is compiled with -ffp-contract=off (the reference's unfused arithmetic), triangulate.hip with contraction.
+// Contraction is set per translation unit, so the helpers the two files share as headers (jacobi.hpp, tri_angle.hpp) are
+// compiled under each file's own setting: one source, each file's rounding as it was.
 // No atomics, no cross-lane arithmetic: a point's result does not depend on what else is in the launch.
 #include "common.hpp"
+#include "jacobi.hpp"
 #include "tri_angle.hpp"
 #include "../../include/vggsfm_amd_multiview.h"
 
@@ -26,55 +28,8 @@ namespace {
 constexpr double kMvPi = 3.141592653589793;
 constexpr double kMvEps = 1e-12;          // the eps default of calculate_triangulation_angle_batched (the reduced pass)
 
-// eigenvector of the smallest eigenvalue of the symmetric 4x4 (a: 00 01 02 03 11 12 13 22 23 33): cyclic Jacobi
-__device__ __forceinline__ void mv_smallest_eigvec4(const double* a, double* v) {
-  double A[4][4] = {{a[0], a[1], a[2], a[3]}, {a[1], a[4], a[5], a[6]}, {a[2], a[5], a[7], a[8]}, {a[3], a[6], a[8], a[9]}};
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-#pragma unroll 1
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    double off = 0.0, dsum = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      dsum += fabs(A[p][p]);
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) off += fabs(A[p][q]);
-    }
-    if (!(off > 1e-300) || off <= 1e-24 * dsum) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = A[p][q];
-        if (fabs(apq) > 1e-300) {
-          const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-          const double t = ((theta >= 0.0) ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double akp = A[k][p], akq = A[k][q];
-            A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double apk = A[p][k], aqk = A[q][k];
-            A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double vkp = V[k][p], vkq = V[k][q];
-            V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
-          }
-        }
-      }
-    }
-  }
-  int best = 0;
-  double bv = A[0][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (A[k][k] < bv) { bv = A[k][k]; best = k; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (best == 0) ? V[k][0] : (best == 1) ? V[k][1] : (best == 2) ? V[k][2] : V[k][3];
-}
+constexpr int kMvSweeps4 = 16;            // the 4x4 Jacobi of mv_solve_kernel: at most this many sweeps ...
+constexpr double kMvTol4 = 1e-24;         // ... done at this ratio of the off-diagonal sum to the diagonal's
 
 // triangulation_helpers.py:503-519: law of cosines on squared lengths, min(theta, pi - theta), degrees
 __device__ __forceinline__ double mv_angle_deg(double r1, double r2, double bsq, double eps) {
@@ -148,7 +103,7 @@ __global__ __launch_bounds__(64) void mv_solve_kernel(const MvSolve a) {
     invalid = true;
   } else {
     double v[4];
-    mv_smallest_eigvec4(m, v);
+    smallest_eigvec4<kMvSweeps4>(m, kMvTol4, v);
     X0 = v[0] / v[3]; X1 = v[1] / v[3]; X2 = v[2] / v[3];
     invalid = false;
     if (a.out_invalid) {
@@ -168,10 +123,7 @@ __global__ __launch_bounds__(256) void mv_centers_kernel(const double* __restric
                                                          double* __restrict__ centers) {
   const long s = (long)blockIdx.x * 256 + threadIdx.x;
   if (s >= count) return;
-  const double* P = cams + 12 * s;
-  centers[3 * s] = -(P[0] * P[3] + P[4] * P[7] + P[8] * P[11]);
-  centers[3 * s + 1] = -(P[1] * P[3] + P[5] * P[7] + P[9] * P[11]);
-  centers[3 * s + 2] = -(P[2] * P[3] + P[6] * P[7] + P[10] * P[11]);
+  camera_centre(cams + 12 * s, centers + 3 * s);
 }
 
 // per point: the largest angle over all camera pairs (FLAG_ONLY: whether some pair reaches `thr`, scan stops wave-wide once

@@ -15,7 +15,7 @@
 //   pairs   one thread per camera pair; the two relative poses live in registers
 // A masked-out point (mask or weight 0) is skipped: nothing read from its slots enters a result.
 #include "common.hpp"
-#include "two_view.hpp"
+#include "jacobi.hpp"
 #include "kabsch3.hpp"
 #include "support.hpp"
 #include "../../include/vggsfm_amd_sim3.h"
@@ -30,6 +30,7 @@ constexpr int kPts = 8;              // points per thread of the score pass, in 
 constexpr int kScorePart = 256 * kPts;  // points per workgroup of the score pass
 constexpr int kMaxGridYZ = 65535;
 static_assert(kFitMaxParts <= 256, "ordered_partials holds one partial per thread of a workgroup");
+constexpr int kSweepsScatter = 10;   // Jacobi sweeps of the 3x3 source scatter (sym3_eigenvalues)
 constexpr double kCollinear = 1e-12; // second / first eigenvalue of the source scatter at or below which a set is collinear
 constexpr double kAngleEps = 1e-15;  // the reference's clamp (metric.py rotation_angle, compare_translation_by_angle)
 constexpr double kDegrees = 57.295779513082320876798154814105;
@@ -99,20 +100,7 @@ __device__ __forceinline__ void add_moment_terms(const double* s, const double* 
 // eigenvalues of the symmetric 3x3 matrix (xx, xy, xz, yy, yz, zz) by cyclic Jacobi, in descending order
 __device__ inline void sym3_eigenvalues(const double* S, double* ev) {
   double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
-  for (int sw = 0; sw < kSweeps3; ++sw) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        double c, s;
-        jacobi_cs(A[p][p], A[q][q], A[p][q], c, s);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { const double cp = A[i][p], cq = A[i][q]; A[i][p] = c * cp - s * cq; A[i][q] = s * cp + c * cq; }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { const double rp = A[p][j], rq = A[q][j]; A[p][j] = c * rp - s * rq; A[q][j] = s * rp + c * rq; }
-      }
-    }
-  }
+  jacobi_sym3<kSweepsScatter, false>(A, nullptr);
   const double a = A[0][0], b = A[1][1], c = A[2][2];
   ev[0] = fmax(a, fmax(b, c));
   ev[2] = fmin(a, fmin(b, c));

@@ -1,10 +1,18 @@
-// The triangulation angle of two views at a point, from squared lengths, as the reference computes it.
+// The triangulation angle of two views at a point, from squared lengths, as the reference computes it, and the projection
+// centres it is measured between.
 #pragma once
 #include "common.hpp"
 
 namespace vgg {
 
 constexpr double kPi = 3.141592653589793;
+
+// projection centre -R^T t of the 3x4 pose P (triangulation_helpers.py:531)
+__device__ __forceinline__ void camera_centre(const double* __restrict__ P, double* __restrict__ out) {
+  out[0] = -(P[0] * P[3] + P[4] * P[7] + P[8] * P[11]);
+  out[1] = -(P[1] * P[3] + P[5] * P[7] + P[9] * P[11]);
+  out[2] = -(P[2] * P[3] + P[6] * P[7] + P[10] * P[11]);
+}
 
 __device__ __forceinline__ double sqnorm3(double a, double b, double c) {
   const double n = sqrt(a * a + b * b + c * c);   // the reference squares a norm: (x).norm(dim=-1) ** 2

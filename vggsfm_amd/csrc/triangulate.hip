@@ -23,6 +23,7 @@
 // launches with 2*pi+1e-6 (true whenever any hypothesis of the chunk has no inlier) and re-launches with
 // the measured maximum in the pathological case that it is not.
 #include "common.hpp"
+#include "jacobi.hpp"
 #include "tri_angle.hpp"
 
 namespace vgg {
@@ -36,63 +37,9 @@ constexpr int kTab = 4;    // doubles per view in LDS: unit ray (3), invalid fla
 
 struct Sym4 { double a[10]; };  // 00 01 02 03 11 12 13 22 23 33
 
-// eigenvector of the smallest eigenvalue of a symmetric 4x4 matrix: cyclic Jacobi, in registers
-__device__ __forceinline__ void smallest_eigvec4(const Sym4& m, double* v) {
-  double A[4][4] = {{m.a[0], m.a[1], m.a[2], m.a[3]}, {m.a[1], m.a[4], m.a[5], m.a[6]},
-                    {m.a[2], m.a[5], m.a[7], m.a[8]}, {m.a[3], m.a[6], m.a[8], m.a[9]}};
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-#pragma unroll 1
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    double off = 0.0, dsum = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      dsum += fabs(A[p][p]);
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) off += fabs(A[p][q]);
-    }
-    if (!(off > 1e-300) || off <= 1e-22 * dsum) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = A[p][q];
-        if (fabs(apq) > 1e-300) {
-          const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-          const double t = ((theta >= 0.0) ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double akp = A[k][p], akq = A[k][q];
-            A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double apk = A[p][k], aqk = A[q][k];
-            A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double vkp = V[k][p], vkq = V[k][q];
-            V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
-          }
-        }
-      }
-    }
-  }
-  int best = 0;
-  double bv = A[0][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (A[k][k] < bv) { bv = A[k][k]; best = k; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (best == 0) ? V[k][0] : (best == 1) ? V[k][1] : (best == 2) ? V[k][2] : V[k][3];
-}
+constexpr int kTriSweeps4 = 12;      // the Jacobi fallback of smallest_eigvec4_fast: at most this many sweeps ...
+constexpr double kTriTol4 = 1e-22;   // ... done at this ratio of the off-diagonal sum to the diagonal's
 
-#ifndef VGG_TRI_EIG
-#define VGG_TRI_EIG 1        // 1 = shifted inverse iteration (Jacobi only where it does not converge), 0 = cyclic Jacobi always
-#endif
-#ifndef VGG_TRI_FAST_ERR
-#define VGG_TRI_FAST_ERR 1   // 1 = one reciprocal per view instead of three divisions, series for acos next to 1
-#endif
 #ifndef VGG_TRI_OCC
 #define VGG_TRI_OCC 2        // wavefronts per SIMD the kernel is compiled for (register budget 512 / VGG_TRI_OCC)
 #endif
@@ -112,28 +59,19 @@ __device__ __forceinline__ void smallest_eigvec4(const Sym4& m, double* v) {
 // Up to kInvRounds factorisations; what is still moving after that (lambda_1 = lambda_2 to rounding: no parallax at all)
 // goes to the Jacobi.  `live` = the lane's result is used (a dead lane must not send its wavefront into the fallback).
 constexpr int kInvIt = 6, kInvRounds = 6;
-#ifndef VGG_TRI_FASTDIV
-#define VGG_TRI_FASTDIV 1    // 1 = the pivot reciprocals and the normalisation of the inverse iteration from the hardware estimates +
-#endif                       //     Newton steps (1 ulp) instead of IEEE divisions / sqrt + division: the iteration converges to the same
-                             //     vector (its tolerance is 1e-14), four divisions and one per step are ~200 instructions per solve
+// The pivot reciprocals and the normalisation of the inverse iteration come from the hardware estimates + Newton steps (1 ulp),
+// not from IEEE divisions / sqrt + division: the iteration converges to the same vector (its tolerance is 1e-14), and four
+// divisions and one per step are ~200 instructions per solve
 __device__ __forceinline__ double tri_rcp(double x) {
-#if VGG_TRI_FASTDIV
   double r = __builtin_amdgcn_rcp(x);
   r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
   return __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-#else
-  return 1.0 / x;
-#endif
 }
 __device__ __forceinline__ double tri_rsqrt(double x) {
-#if VGG_TRI_FASTDIV
   double r = __builtin_amdgcn_rsq(x);
   const double h = 0.5 * x;
   r = r * __builtin_fma(-h * r, r, 1.5);
   return r * __builtin_fma(-h * r, r, 1.5);
-#else
-  return 1.0 / sqrt(x);
-#endif
 }
 __device__ __forceinline__ bool smallest_eigvec4_invit(const Sym4& m, double* v, bool live) {
   const double tr = m.a[0] + m.a[4] + m.a[7] + m.a[9];
@@ -189,7 +127,6 @@ __device__ __forceinline__ bool smallest_eigvec4_invit(const Sym4& m, double* v,
 __device__ unsigned long long g_tri_stats[4];       // measurement builds: eigen-solves, fallbacks, waves with a fallback
 #endif
 __device__ __forceinline__ void smallest_eigvec4_fast(const Sym4& m, double* v, bool live) {
-#if VGG_TRI_EIG
   const bool done = smallest_eigvec4_invit(m, v, live);
 #ifdef VGG_TRI_STATS
   atomicAdd(&g_tri_stats[0], 1ull);
@@ -200,23 +137,16 @@ __device__ __forceinline__ void smallest_eigvec4_fast(const Sym4& m, double* v, 
   //  two smallest eigenvalues agree to rounding.  Dropping it is worth 0.2 ms of 18 at configs[2] and changed ONE mask bit in
   //  4.9 million there (such a hypothesis can still pass the triangulation-angle test): kept, so that the masks are what the
   //  Jacobi-only kernel of rounds 1-3 produced on every golden and at configs[2])
-  if (!done) smallest_eigvec4(m, v);
-#else
-  smallest_eigvec4(m, v);
-#endif
+  if (!done) smallest_eigvec4<kTriSweeps4>(m.a, kTriTol4, v);
 }
 
 // acos for the candidate inliers, whose cosine is within ~1e-3 of 1: acos(1 - u) = sqrt(2u) (1 + u/12 + 3u^2/160 + 5u^3/896
 // + 35u^4/18432 + O(u^5)); u = 1 - c is exact there (Sterbenz), the truncation error at u = 1e-3 is 7e-19.
 __device__ __forceinline__ double acos_near_one(double c) {
-#if VGG_TRI_FAST_ERR
   const double u = 1.0 - c;
   if (u > 1.0e-3) return acos(c);
   const double p = 1.0 + u * (1.0 / 12.0 + u * (3.0 / 160.0 + u * (5.0 / 896.0 + u * (35.0 / 18432.0))));
   return sqrt(u + u) * p;
-#else
-  return acos(c);
-#endif
 }
 
 // DLT matrix T^T T of one view, T = P - r (r^T P) for the unit ray r (3x4 rows of the projection matrix P)
@@ -241,16 +171,11 @@ __device__ __forceinline__ double view_error(const double* __restrict__ P, doubl
   const double y1 = P[4] * X0 + P[5] * X1 + P[6] * X2 + P[7];
   const double y2 = P[8] * X0 + P[9] * X1 + P[10] * X2 + P[11];
   depth = y2;
-#if VGG_TRI_FAST_ERR
   // one reciprocal square root instead of the reference's square root and three divisions: the cosine moves by <= 2 ulp, the
   // angle of a candidate inlier by ~5e-15 rad -- a decision changes only where |error - threshold| is below that (the goldens
   // compare every mask bit).  (max(|y|, 1e-12) of the reference = max(|y|^2, 1e-24) under the root.)
   const double rn = rsqrt(fmax(y0 * y0 + y1 * y1 + y2 * y2, 1e-24));
   double c = (ray0 * (y0 * rn) + ray1 * (y1 * rn)) + ray2 * (y2 * rn);
-#else
-  const double n = fmax(sqrt(y0 * y0 + y1 * y1 + y2 * y2), 1e-12);
-  double c = (ray0 * (y0 / n) + ray1 * (y1 / n)) + ray2 * (y2 / n);
-#endif
   is_nan = (c != c);
   c = fmin(fmax(c, -1.0), 1.0);
   if (!(c >= cos_gate)) return 4.0;             // cannot be an inlier (also NaN): skip acos
@@ -283,74 +208,12 @@ __device__ __forceinline__ bool any_pair_angle(const double* __restrict__ center
 }
 
 // Walk over the visible views of a track; the body gets the projection matrix (scalar registers), the unit ray, the view and
-// its position in the list.  -DVGG_TRI_PIPE=1 (round 6, MEASURED SLOWER, off): the matrix of the NEXT view already requested
-// while the body runs.  The view loops are wave-uniform -- the index comes out of LDS (v_readfirstlane), the matrix through
-// scalar loads: a dependent chain of an LDS round trip and a scalar-memory round trip in front of every view, which the
-// compiler cannot move across the loop's back edge, and 38 % of a wavefront's resident time is s_waitcnt
-// (profiles/r05_pmc_sq_tri.json).  With two NAMED matrix sets per trip (no copies between stages, which is what sank the
-// round-4 attempt), the index and the ray fetched one step further ahead and ONE wait per view placed behind the body (LDS
-// reads and scalar loads share lgkmcnt and scalar loads return out of order: any wait for LDS data waits for every scalar load
-// in flight) the kernel takes 13.3 ms against 11.85 at configs[2] and 1.38 against 1.34 at configs[1]
-// (profiles/r06_ab_tri_c3.jsonl; masks and points identical): the extra vector registers (rays and index of two views in
-// flight: 52 B of scratch at four hypotheses per lane) and the serialising waits cost more than the chain they hide -- the
-// second resident wavefront covers it already.
+// its position in the list.  The loop is wave-uniform and plain: the index comes out of LDS (v_readfirstlane), the matrix through
+// scalar loads, and nothing is requested ahead of its view.  The chain of two round trips in front of every view is covered by
+// the second resident wavefront; a software pipeline that hides it was measured slower.
 // body(const double (&P)[12], double ray0, double ray1, double ray2, int s, int k)
-#ifndef VGG_TRI_PIPE
-#define VGG_TRI_PIPE 0
-#endif
 template <class F>
 __device__ __forceinline__ void for_each_view(const double* __restrict__ ext, const double* tab, const int* vlist, int nv, F&& body) {
-#if VGG_TRI_PIPE
-  if (nv <= 0) return;
-  double pa[12], pb[12];
-  auto request = [&](double (&p)[12], int s) __attribute__((always_inline)) {
-    const double* P = ext + 12 * s;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) p[i] = P[i];
-  };
-  // LDS reads and scalar loads share one counter (lgkmcnt) and scalar loads return out of order, so ANY wait for LDS data also
-  // waits for every scalar load in flight.  The schedule per view k (matrix set A; set B = view k + 1 is in flight):
-  //   [index of view k + 2 -> scalar; LDS reads of its ray and of the index of view k + 3 issued]  [body(k): no memory access]
-  //   [ONE wait: the ray, the index, set B -- all requested a whole body ago]  [set A requested for view k + 2]
-  // and the same with the sets swapped: a matrix has the body of the view in between to arrive, the two LDS round trips
-  // (index, then ray) are hidden behind a body as well, and the body gets the ray as values.
-  struct Ray { double r0, r1, r2; };
-  auto clampk = [&](int k) { return min(k, nv - 1); };
-  auto ray_of = [&](int sv) __attribute__((always_inline)) -> Ray {
-    const double* t = tab + sv * kTab;
-    Ray r; r.r0 = t[0]; r.r1 = t[1]; r.r2 = t[2];
-    return r;
-  };
-  // prologue: views 0 and 1
-  int sa = __builtin_amdgcn_readfirstlane(vlist[0]), sb = __builtin_amdgcn_readfirstlane(vlist[clampk(1)]);
-  Ray ra = ray_of(sa), rb = ray_of(sb);
-  int idx_next = vlist[clampk(2)];                      // (vector register; becomes a scalar one step later)
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra.r0), "+v"(ra.r1), "+v"(ra.r2), "+v"(rb.r0), "+v"(rb.r1), "+v"(rb.r2), "+v"(idx_next) : : "memory");
-  request(pa, sa);
-  request(pb, sb);
-  int k = 0;
-  for (; k + 1 < nv; k += 2) {
-    {
-      const int s2 = __builtin_amdgcn_readfirstlane(idx_next);
-      Ray r2 = ray_of(s2);
-      int idx3 = vlist[clampk(k + 3)];
-      body(pa, ra.r0, ra.r1, ra.r2, sa, k);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r2.r0), "+v"(r2.r1), "+v"(r2.r2), "+v"(idx3) : : "memory");
-      request(pa, s2);
-      sa = s2; ra = r2; idx_next = idx3;
-    }
-    {
-      const int s3 = __builtin_amdgcn_readfirstlane(idx_next);
-      Ray r3 = ray_of(s3);
-      int idx4 = vlist[clampk(k + 4)];
-      body(pb, rb.r0, rb.r1, rb.r2, sb, k + 1);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r3.r0), "+v"(r3.r1), "+v"(r3.r2), "+v"(idx4) : : "memory");
-      request(pb, s3);
-      sb = s3; rb = r3; idx_next = idx4;
-    }
-  }
-  if (k < nv) body(pa, ra.r0, ra.r1, ra.r2, sa, k);
-#else
   for (int k = 0; k < nv; ++k) {
     const int s = __builtin_amdgcn_readfirstlane(vlist[k]);
     double p[12];
@@ -359,7 +222,6 @@ __device__ __forceinline__ void for_each_view(const double* __restrict__ ext, co
     const double* t = tab + s * kTab;
     body(p, t[0], t[1], t[2], s, k);
   }
-#endif
 }
 
 struct Cand { double e; int n; };   // mean inlier error (or 2*pi) and inlier count of one hypothesis
@@ -797,10 +659,7 @@ __device__ __forceinline__ void view_dlt_matrix(const double* __restrict__ P, do
 __global__ void view_centers_kernel(const double* __restrict__ ext, int S, double* __restrict__ centers) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
-  const double* P = ext + 12 * s;
-  centers[3 * s] = -(P[0] * P[3] + P[4] * P[7] + P[8] * P[11]);
-  centers[3 * s + 1] = -(P[1] * P[3] + P[5] * P[7] + P[9] * P[11]);
-  centers[3 * s + 2] = -(P[2] * P[3] + P[6] * P[7] + P[10] * P[11]);
+  camera_centre(ext + 12 * s, centers + 3 * s);
 }
 
 __global__ __launch_bounds__(256) void triangulate_pairs_kernel(const double* __restrict__ ext,

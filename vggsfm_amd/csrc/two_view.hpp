@@ -1,6 +1,6 @@
 // Device code shared by the two-view estimators (fundamental.hip, essential.hip): the 3x3 product, the squared Sampson
-// distance, the Jacobi rotation, the fixed-order block reduction, the scoring kernel, the selected-hypothesis load and the
-// 9x9 Gram accumulation and reduction.  Compiled without floating-point contraction in both files.  Entries: vgg_fmat_score
+// distance, the scoring kernel, the selected-hypothesis load and the 9x9 Gram accumulation and reduction (the matrix's
+// eigen-solve is jacobi.hpp's, the fixed-order block reduction common.hpp's).  Compiled without floating-point contraction in both files.  Entries: vgg_fmat_score
 // and vgge_emat_score stay apart and launch the one two_view_score_kernel; vgg_fmat_residuals (fundamental.hip) is shared
 // as it is -- it gives the residuals of either flow's winner.
 #pragma once
@@ -11,15 +11,6 @@ namespace vgg {
 constexpr double kBig = 1e6;         // residual of an invalid match
 constexpr int kSweeps9 = 10;         // cyclic Jacobi sweeps of a 9x9 matrix (fmat8_kernel, five_point_from_gram)
 constexpr int kHypPerWave = 4;       // hypotheses scored per sweep of a wavefront: the points are read once for all of them
-
-__device__ inline void jacobi_cs(double app, double aqq, double apq, double& c, double& s) {
-  const bool rot = apq != 0.0;
-  const double tau = (aqq - app) / (2.0 * (rot ? apq : 1.0));
-  const double t = ((tau >= 0.0) ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-  const double cc = 1.0 / sqrt(1.0 + t * t);
-  c = rot ? cc : 1.0;
-  s = rot ? t * cc : 0.0;
-}
 
 // C = A B (3x3 row-major), terms added left to right
 __device__ __forceinline__ void mat3_ab(const double* A, const double* B, double* C) {
@@ -40,25 +31,6 @@ __device__ inline double sampson_sq(const double* __restrict__ F, double u1, dou
   const double den = (l0 * l0 + l1 * l1) + (m0 * m0 + m1 * m1);
   const double r = (num * num) / den;
   return isfinite(r) ? r : kBig;
-}
-
-// fixed-order reduction of Q quantities over the 256 threads: halving tree (t, t + 128), (t, t + 64), ...
-template <int Q>
-__device__ inline void block_tree_sum(double (*red)[256], const double* val, double* out) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) red[q][tid] = val[q];
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) red[q][tid] = red[q][tid] + red[q][tid + st];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < Q; ++q) out[q] = red[q][0];
-  __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------------------ scoring
