@@ -26,12 +26,18 @@ class Triangulator(nn.Module):
     def forward(self, pred_cameras, pred_tracks, pred_vis, images, preliminary_dict, pred_score=None,
                 init_max_reproj_error=0.5, BA_iters=2, shared_camera=False, max_reproj_error=4, init_tri_angle_thres=16,
                 min_valid_track_length=3, robust_refine=2, extract_color=True, camera_type="SIMPLE_PINHOLE"):
-        """Reference: triangulator.py:44-363."""
+        """Reference: triangulator.py:44-363.  pred_cameras=None: the prior is ``geometric_camera_prior`` of the tracks."""
         device = pred_tracks.device
         B, S, _, H, W = images.shape
         _, _, N, _ = pred_tracks.shape
         assert B == 1
         image_size = torch.tensor([W, H], dtype=pred_tracks.dtype, device=device)
+        if pred_cameras is None:
+            # no learned prior: cameras from the tracks themselves (two_view_geo/camera_prior.py)
+            from ..two_view_geo.camera_prior import geometric_camera_prior
+            pred_cameras = geometric_camera_prior(pred_tracks, pred_vis, W, H, tracks_score=pred_score,
+                                                  preliminary_dict=preliminary_dict, camera_type=camera_type,
+                                                  shared_camera=shared_camera)
         extrinsics, intrinsics = get_EFP(pred_cameras, image_size, B, S)
         extrinsics = extrinsics.double()
         inlier_fmat = preliminary_dict["fmat_inlier_mask"]

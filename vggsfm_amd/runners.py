@@ -2,7 +2,8 @@
 device: two-view stage -> Triangulator -> optional dense extra points -> frame filtering / re-ordering -> back to the
 original resolution -> the ``predictions`` dict the rest of the runner (saving, visualisation, dense depth) reads.
 
-The learned parts stay with the caller: ``pred_cameras`` comes from the camera predictor, ``pred_track`` / ``pred_vis``
+The learned parts stay with the caller: ``pred_cameras`` comes from the camera predictor (None: the cameras are built from
+the tracks, ``vggsfm_amd.two_view_geo.geometric_camera_prior``), ``pred_track`` / ``pred_vis``
 / ``pred_score`` from the tracker, and the dense pass asks the caller's tracker for the grid tracks through
 ``extra_tracker`` (the reference calls ``predict_tracks`` there, runner.py:676-694).  Option names are the reference's
 cfg keys (cfgs/demo.yaml)."""
@@ -138,7 +139,8 @@ class GeometryRunner:
         predictions = {}
         if image_paths is None:
             image_paths = [f"image_{s}" for s in range(S)]
-        _, preliminary_dict = estimate_preliminary_cameras(pred_track, pred_vis, W, H, tracks_score=pred_score, decompose=False,
+        _, preliminary_dict = estimate_preliminary_cameras(pred_track, pred_vis, W, H, tracks_score=pred_score,
+                                                           decompose=pred_cameras is None,    # (None: the prior needs them)
                                                            max_error=cfg.fmat_thres, loopresidual=True,
                                                            max_ransac_iters=cfg.max_ransac_iters, lo_num=cfg.lo_num)
         (extrinsics_opencv, intrinsics_opencv, extra_params, points3D, points3D_rgb, reconstruction, valid_frame_mask,

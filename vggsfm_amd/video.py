@@ -172,7 +172,9 @@ class VideoGeometry:
     ``point_dict`` / ``frame_dict`` state held in a device-resident :class:`TrackTable`:
 
         camera_prior(frame_from, frame_to) -> (frame_to - frame_from, 3, 4) predicted extrinsics (OpenCV), any gauge
-            -- the reference's ``average_camera_prediction`` over (last window, next window), video_runner.py:662-667
+            -- the reference's ``average_camera_prediction`` over (last window, next window), video_runner.py:662-667;
+            None, without a `camera_predictor` either: the new frames start at the last registered pose and are posed by
+            P3P on the carried-over points (``use_pnp`` forced on)
         track_existing(frame_from, frame_to, query_uv (P,2)) -> (tracks (S,P,2), vis (S,P))
             -- ``predict_tracks`` with the carried-over points as queries in frame_from, video_runner.py:1133-1146
         track_new(frame_from, frame_to) -> (tracks (S,N,2), vis (S,N), score (S,N) | None)
@@ -256,12 +258,16 @@ class VideoGeometry:
         print(f"Processing window from {start_idx} to {end_idx}")
         camera_prior = camera_prior or self.camera_prior
         if camera_prior is None:
-            raise ValueError("no camera_prior: pass one, or construct VideoGeometry with camera_predictor and images")
-        # predicted cameras of (last window, next window), aligned to the last window's reconstruction
-        pred_extri = camera_prior(last_start_idx, end_idx).to(self.device, torch.float64)
-        last_extri = t.extri[last_start_idx:start_idx].to(torch.float64)
-        rel_r, rel_t, rel_s = align_camera_extrinsics(pred_extri[:last_window_size], last_extri)
-        aligned_next = apply_transformation(pred_extri[last_window_size:], rel_r, rel_t, rel_s)
+            # no learned prior: every new frame starts at the last registered pose and is posed by P3P on the carried-over
+            # points (the reference's own `use_pnp` branch, video_runner.py:991-998)
+            aligned_next = t.extri[start_idx - 1:start_idx].to(torch.float64).repeat(window_size, 1, 1)
+            use_pnp = True
+        else:
+            # predicted cameras of (last window, next window), aligned to the last window's reconstruction
+            pred_extri = camera_prior(last_start_idx, end_idx).to(self.device, torch.float64)
+            last_extri = t.extri[last_start_idx:start_idx].to(torch.float64)
+            rel_r, rel_t, rel_s = align_camera_extrinsics(pred_extri[:last_window_size], last_extri)
+            aligned_next = apply_transformation(pred_extri[last_window_size:], rel_r, rel_t, rel_s)
         # prepare_window_data: carried-over points tracked through (start_idx - 1 .. end_idx)
         ids, xyz, uv = self.select_existing_points(start_idx - 1)
         tracks_e, vis_e = track_existing(start_idx - 1, end_idx, uv)
