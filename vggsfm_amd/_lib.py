@@ -215,11 +215,16 @@ def lib():
         if int(L.vgg_abi_sizeof(which)) != ctypes.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {int(L.vgg_abi_sizeof(which))} in the library and "
                                f"{ctypes.sizeof(st)} in the binding -- header and binding are out of step")
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    bind(L, SIGNATURES)
     _lib = L
     return L
+
+
+def bind(L, signatures):
+    """Give every entry of a loaded library the C types of its row ({name: (return type, parameter types)})."""
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 def check(rc, what):

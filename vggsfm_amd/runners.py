@@ -198,6 +198,31 @@ class GeometryRunner:
                            preliminary_dict=preliminary_dict)
         return predictions
 
+    # ------------------------------------------------------------------ frames in, reconstruction out (no learned part)
+    def reconstruct_from_frames(self, images, query_frame=0, max_query_pts=2048, bound_bboxes=None, **tracker_options):
+        """The whole sparse reconstruction from frames alone: images (1,S,3,H,W) float32 in [0, 1] -> the corners of
+        `query_frame` tracked through the sequence (vggsfm_amd.klt.KLTTracker, `tracker_options` are its options) ->
+        sparse_reconstruct_from_tracks without predicted cameras, at the resolution of the frames.  With
+        cfg.extra_pt_pixel_interval > 0 the tracker also serves the dense extra points (bound_bboxes (1,S,4), default: the
+        whole frame).  predictions["tracker"] keeps the tracker."""
+        from .klt import KLTTracker
+
+        if images.dim() == 4:
+            images = images[None]
+        S, H, W = images.shape[1], images.shape[-2], images.shape[-1]
+        tracker = KLTTracker(images, **tracker_options)
+        pred_track, pred_vis, pred_score = tracker.predict_tracks(query_frame=query_frame, max_query_pts=max_query_pts)
+        extra = None
+        if self.cfg.extra_pt_pixel_interval > 0:
+            extra = tracker.extra_tracker
+            if bound_bboxes is None:
+                bound_bboxes = torch.tensor([0.0, 0.0, W - 1.0, H - 1.0], device=images.device).expand(1, S, 4)
+        predictions = self.sparse_reconstruct_from_tracks(None, pred_track, pred_vis, pred_score, images,
+                                                          back_to_original_resolution=False, extra_tracker=extra,
+                                                          bound_bboxes=bound_bboxes)
+        predictions["tracker"] = tracker
+        return predictions
+
     # ------------------------------------------------------------------ dense depth (runner.py:744-814)
     def extract_sparse_depth_and_point_from_reconstruction(self, predictions):
         """runner.py:744-772 with one projection kernel (vgg_sparse_depth) instead of the per-observation loop.  Sets
