@@ -373,9 +373,6 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
  * entries[e][0] = the entry's point.
  * Bit 2 (value | 4; A/B measurements and tests): keep the glue of an LM iteration as separate launches -- tile sums, assembly,
  * preparation, step sums -- instead of the merged ones; the same bits either way.
- * Bit 3 (value | 8; A/B measurements): keep the back-substitution sweep of point_step over full Jacobians, with the model cost
- * change summed observation by observation -- instead of the directional sweep with the cameras' share of the model cost
- * change taken from U | g; the same iteration up to rounding.
  * Host-side state (the only one of this API): vgg_ba_begin notes, per WORKSPACE ADDRESS, that the preparation launch is still
  * due in front of the first point pass, and whether every camera group has a diagonal tile -- for which it copies the tile
  * table (16 bytes per tile) to the host and synchronises the stream ONCE per solve.  The table holds the 64 most recently begun

@@ -1,6 +1,7 @@
 """Same-box A/B of host-side launch choices on the bench workload (BASELINE configs[2] by default): the scene is built once,
-every variant = a set of environment switches read by vggsfm_amd.ba.compile_problem (VGGSFM_TILE_BACKFILL, VGGSFM_TILE_WGS,
-...) -> ms per LM iteration + per-kernel HIP-event times, variants interleaved over `--rounds` rounds (drift shows up as a
+every variant = a set of environment switches read by vggsfm_amd.ba behind VGGSFM_AMD_DEBUG_HOOKS=1 (VGGSFM_TILE_WGS,
+VGGSFM_TILE_ORDER, VGGSFM_TILE_FIXED_COST, VGGSFM_TILE_TOP_UP, VGGSFM_QUAD_SORT_WINDOW, VGGSFM_SORT_POINTS,
+VGGSFM_LEGACY_GLUE) -> ms per LM iteration + per-kernel HIP-event times, variants interleaved over `--rounds` rounds (drift shows up as a
 difference between the rounds of one variant).  A different library (built with other -D switches) is selected for the
 whole process with VGGSFM_AMD_LIB.
 A variant key RCCL=1 (RCCL=2) runs the iteration with the collectives of a ONE-RANK "nccl" communicator between the phases

@@ -174,13 +174,10 @@ class DeviceProblem:
 
 
 # Measurement hooks.  The product path reads NO environment variable unless VGGSFM_AMD_DEBUG_HOOKS=1 is set (the A/B harness
-# scripts/prof/ab_c3.py sets it): then VGGSFM_QUAD_SORT_WINDOW, VGGSFM_TILE_TOP_UP, VGGSFM_TILE_ORDER, VGGSFM_TILE_COST_MODE,
-# VGGSFM_TILE_FIXED_COST, VGGSFM_TILE_POS_WEIGHT, VGGSFM_SORT_POINTS, VGGSFM_TILE_WGS and VGGSFM_TILE_BACKFILL override the
-# constants below, and VGGSFM_LEGACY_GLUE=1 keeps the separate glue launches of an LM iteration (solve), all read per call
-# (A/B runs switch them in-process).  Every one of them changes the SCHEDULE of the work,
-# never a sum: results are bit-identical across their values (tests/test_gpu_ba.py).  The exception is VGGSFM_LEGACY_STEP=1
-# (solve): the back-substitution sweep over full Jacobians, which rounds the candidate points and the model cost change
-# differently from the directional sweep.
+# scripts/prof/ab_c3.py sets it): then VGGSFM_QUAD_SORT_WINDOW, VGGSFM_TILE_TOP_UP, VGGSFM_TILE_ORDER, VGGSFM_TILE_FIXED_COST,
+# VGGSFM_SORT_POINTS and VGGSFM_TILE_WGS override the constants below, and VGGSFM_LEGACY_GLUE=1 keeps the separate glue launches
+# of an LM iteration (solve), all read per call (A/B runs switch them in-process).  Every one of them changes the SCHEDULE of
+# the work, never a sum: results are bit-identical across their values (tests/test_gpu_ba.py).
 def _hook(name, default=None):
     if os.environ.get("VGGSFM_AMD_DEBUG_HOOKS") != "1":
         return default
@@ -199,28 +196,27 @@ TILE_TOP_UP = True           # hand the slots the chunk-size search leaves empty
 TILE_ORDER = "sparse_first"        # launch order of the tiles: "plain" = (gI, gJ); "dense_first" / "sparse_first" (build_schur_tiles)
 TILE_ORDERS = ("plain", "dense_first", "sparse_first")
 TILE_ORDERS_EXPERIMENTAL = ("stride", "sdm", "msd", "dsm")     # round-5 A/B variants (profiles/r05_ab_tile_order_c3.jsonl), hooks only
-TILE_POSITION_WEIGHT = 0.0        # see build_schur_tiles: extra cost of a tile per unit of launch position (0 = off: with every slot filled
-#                                   the sweep 0 .. 0.45 stayed inside the run-to-run noise, profiles/r05_ab_tile_fixed_cost_c3.jsonl)
+
+
+def _block_slot_bits(block_rows, group=GROUP):
+    """Per 16-row block b of a tile side, the camera slots with rows in it as a bit mask (block_slot_bits<BD> in csrc/ba.hip):
+    slots 16 b // block_rows .. (16 b + 15) // block_rows.  The tile kernels run block b when one of those cameras is present."""
+    return [((2 << min(group - 1, (16 * b + 15) // block_rows)) - 1) & ~((1 << ((16 * b) // block_rows)) - 1)
+            for b in range(block_rows * group // 16)]
 
 
 def _entry_cost(qmask, diag, bd, group=GROUP):
     """Cost model of one tile entry for the workgroup counts (what schur_tile_kernel spends on the QUAD the entry belongs
     to): TILE_FIXED_COST + 3 x the matrix instructions of the busiest of the four wavefronts, from the quad's presence masks
-    exactly as the kernel skips -- 16-row block b of a side runs when one of the cameras with rows in it (slots 16 b // bd
-    .. (16 b + 15) // bd) is present.  Off-diagonal tile: wavefront (wr, wc) owns the sub-tiles (wr + 2 i, wc + 2 j); diagonal
-    tile: the lower-triangle sub-tiles row by row, dealt round-robin.  qmask (E,) long: maskA | maskB << 16; diag (E,) bool."""
+    exactly as the kernel skips (_block_slot_bits).  Off-diagonal tile: wavefront (wr, wc) owns the sub-tiles (wr + 2 i,
+    wc + 2 j); diagonal tile: the lower-triangle sub-tiles row by row, dealt round-robin.  qmask (E,) long: maskA | maskB << 16;
+    diag (E,) bool."""
     dev = qmask.device
-    nt = bd                                                   # 16 bd rows / 16
-    bits = []
-    for b in range(nt):
-        s0, s1 = (16 * b) // bd, min(group - 1, (16 * b + 15) // bd)
-        bits.append(((2 << s1) - 1) & ~((1 << s0) - 1))
-    bits = torch.tensor(bits, dtype=torch.long, device=dev)
+    bits = torch.tensor(_block_slot_bits(bd, group), dtype=torch.long, device=dev)
+    nt = bits.shape[0]
     ra = ((qmask[:, None] & 0xFFFF) & bits[None]) != 0        # (E, nt) row blocks with a camera
     rb = ((qmask[:, None] >> 16) & bits[None]) != 0
     off = torch.maximum(ra[:, 0::2].sum(1), ra[:, 1::2].sum(1)) * torch.maximum(rb[:, 0::2].sum(1), rb[:, 1::2].sum(1))
-    if _hook("VGGSFM_TILE_COST_MODE") == "mean":                   # measurement hook: the MEAN wavefront instead of the busiest
-        off = (ra.sum(1) * rb.sum(1)).double() / 4.0
     per_wave = torch.zeros((qmask.shape[0], 4), dtype=torch.long, device=dev)
     t = 0
     for r in range(nt):
@@ -233,9 +229,245 @@ def _entry_cost(qmask, diag, bd, group=GROUP):
     return fixed + 3.0 * torch.where(diag, per_wave.max(1).values, off).double()
 
 
+# ---- build_schur_tiles, stage by stage.  Stages 1-5 are torch ops on the problem's device; their per-tile results go to the
+# ---- host in ONE copy, and stages 6-7 (a few hundred tiles at most) are numpy on the host.
+def _tile_sums(values, tile_start, kcounts):
+    """Per-tile sums of a per-entry list that is sorted by tile: differences of a running sum (no second sort and no atomics:
+    an index_add_ of 5 M doubles into ~100 bins cost 2.4 ms of a 10 ms compile at configs[2])."""
+    csum = torch.cumsum(values, 0)
+    last = csum[tile_start + kcounts - 1]
+    return last - torch.where(tile_start > 0, csum[(tile_start - 1).clamp(min=0)], torch.zeros_like(last))
+
+
+def _entry_tile_index(tile_start, kcounts, total):
+    """(tile of every entry, position of the entry inside its tile) of a list sorted by tile."""
+    dev = kcounts.device
+    tile = torch.repeat_interleave(torch.arange(kcounts.shape[0], device=dev), kcounts, output_size=total)
+    return tile, torch.arange(total, device=dev) - tile_start[tile]
+
+
+def _segments(row_ptr, obs_cam, group):
+    """Stage 1: the runs of one point's observations inside one camera group.
+    -> (point, camera group, presence mask -- bit l <=> camera group*16 + l observes the point -- of every segment; obs_slot)."""
+    dev, O, P = obs_cam.device, obs_cam.shape[0], row_ptr.shape[0] - 1
+    counts = (row_ptr[1:] - row_ptr[:-1]).long()
+    obs_pt = torch.repeat_interleave(torch.arange(P, device=dev), counts, output_size=O)   # (output_size: no host read inside)
+    grp = (obs_cam // group).long()
+    is_start = torch.ones(O, dtype=torch.bool, device=dev)
+    is_start[1:] = (obs_pt[1:] != obs_pt[:-1]) | (grp[1:] != grp[:-1])
+    seg_begin = torch.nonzero(is_start).squeeze(1)
+    seg_id = torch.cumsum(is_start.long(), 0) - 1
+    lane = obs_cam.long() % group
+    seg_mask = torch.zeros(seg_begin.shape[0], dtype=torch.long, device=dev).index_add_(0, seg_id, 1 << lane)
+    return obs_pt[seg_begin], grp[seg_begin], seg_mask, (seg_id * group + lane).to(torch.int32)
+
+
+def _sweep_rank(row_ptr, obs_cam, ncam):
+    """Sweep position of a point: all tiles walk the points in the order (first camera, last camera), so that the four
+    entries a workgroup packs along K (a "quad") have about the same presence pattern (the tile kernels skip the 16-row
+    blocks in which none of the four has a camera) and every tile still meets a given point at about the same time."""
+    dev, O, P = obs_cam.device, obs_cam.shape[0], row_ptr.shape[0] - 1
+    has = row_ptr[1:] > row_ptr[:-1]
+    zero = torch.zeros(P, dtype=torch.long, device=dev)
+    first_cam = torch.where(has, obs_cam.long()[row_ptr[:-1].long().clamp(max=O - 1)], zero)
+    last_cam = torch.where(has, obs_cam.long()[(row_ptr[1:].long() - 1).clamp(min=0)], zero)
+    prank = torch.empty(P, dtype=torch.long, device=dev)
+    prank[torch.argsort(first_cam * ncam + last_cam, stable=True)] = torch.arange(P, device=dev)
+    return prank
+
+
+def _entry_pairs(seg_pt, seg_grp, prank, ngroups, nb):
+    """Stage 2: every pair (A, B >= A) of segments of one point, sorted by tile key and, inside a tile, by sweep position.
+    Tile key = batch * 2 nn + diagonal * nn + gI * ngroups + gJ (nn = ngroups^2): batch-major; inside a batch the off-diagonal
+    tiles first, then the diagonal ones (separate launches).  -> (A, B (E,); key, entry count (T,) of every tile)."""
+    dev, P, nseg = seg_pt.device, prank.shape[0], seg_pt.shape[0]
+    pseg_ptr = torch.zeros(P + 1, dtype=torch.long, device=dev)
+    pseg_ptr[1:] = torch.cumsum(torch.bincount(seg_pt, minlength=P), 0)
+    idx = torch.arange(nseg, device=dev)
+    npair = pseg_ptr[seg_pt + 1] - idx
+    total = int(npair.sum().item())
+    A = torch.repeat_interleave(idx, npair, output_size=total)
+    pair_start = torch.cumsum(npair, 0) - npair
+    B = A + (torch.arange(total, device=dev) - pair_start[A])
+    gA, gB = seg_grp[A], seg_grp[B]
+    # batch of a camera group: runs of consecutive groups gI with about equal numbers of entries
+    if nb == 1:                                                     # (one batch: no counts, no host read)
+        batch_of_group = torch.zeros(ngroups, dtype=torch.long, device=dev)
+    else:
+        per_group = torch.bincount(gA, minlength=ngroups).double()
+        cum = torch.cumsum(per_group, 0) - per_group                # entries before group g
+        batch_of_group = torch.clamp((cum * nb / max(float(total), 1.0)).long(), max=nb - 1)   # (per_group.sum() = total)
+        batch_of_group = torch.cummax(batch_of_group, 0).values
+    nn = ngroups * ngroups
+    key = batch_of_group[gA] * (2 * nn) + (gA == gB).long() * nn + gA * ngroups + gB
+    order = torch.argsort(key * P + prank[seg_pt[A]])
+    tkeys, kcounts = torch.unique_consecutive(key[order], return_counts=True)
+    return A[order], B[order], tkeys, kcounts
+
+
+def _experimental_tile_order(order_mode, perm, cls):
+    """TILE_ORDERS_EXPERIMENTAL (round-5 A/B variants, reachable through the hook gate only): `perm` -- the tiles by density
+    inside their launch class `cls` -- with the densities scattered over a launch ("stride") or the density thirds of a
+    launch in another order ("sdm", "msd", "dsm": s = sparse, m = mid, d = dense)."""
+    dev = perm.device
+    ncls = torch.bincount(cls)
+    cstart = torch.cumsum(ncls, 0) - ncls
+    cp = cls[perm]
+    r = torch.arange(perm.shape[0], device=dev) - cstart[cp]
+    if order_mode == "stride":
+        nc = ncls[cp]
+        step = torch.clamp((nc.double().sqrt().long() | 1), min=1)
+        while bool((torch.gcd(step, nc) != 1).any()):
+            step = torch.where(torch.gcd(step, nc) != 1, step + 2, step)
+        return perm[torch.argsort(cstart[cp] + (r * step) % nc, stable=True)]
+    third = torch.clamp((3 * r) // ncls[cp].clamp(min=1), max=2)       # 0 sparse, 1 mid, 2 dense
+    slot = {"sdm": (0, 2, 1), "msd": (1, 0, 2), "dsm": (2, 0, 1)}[order_mode]
+    where = torch.tensor([slot.index(t) for t in range(3)], device=dev)[third]
+    return perm[torch.argsort(cp * 4 + where, stable=True)]
+
+
+def _launch_order(order_mode, A, B, tkeys, kcounts, seg_mask, bits, nn):
+    """Stage 3: LAUNCH ORDER of the tiles by density (round 5).  The workgroups of a launch are resident three (four) to a CU
+    -- positions p, p + CUs, p + 2 CUs -- and the oldest is served first; in (gI, gJ) order neighbouring positions hold tiles
+    of like density.  Ordered by the mean number of 16-row block products of their entries (own patterns), the launch walks
+    from the sparsest tiles to the densest and every CU gets a mix.  Same-box A/B at configs[2]
+    (profiles/r05_ab_tile_order_c3.jsonl): densest first 0.564 / 0.247 ms (off-diagonal / diagonal launch), (gI, gJ) order
+    0.542 / 0.252, SPARSEST FIRST 0.536 / 0.243 -- the default; densities scattered over the launch 0.570 / 0.244.  The sums
+    of a tile do not depend on where it is launched (final costs equal to the last bit).  The runs of the entry list are moved
+    as blocks, without a second sort.  -> (A, B, tkeys, kcounts) in launch order."""
+    dev, total = A.device, A.shape[0]
+    tile_start = torch.cumsum(kcounts, 0) - kcounts
+    nblk = lambda m: ((m[:, None] & bits[None]) != 0).sum(1)
+    dens = _tile_sums((nblk(seg_mask[A]) * nblk(seg_mask[B])).double(), tile_start, kcounts) / kcounts.double()
+    cls = tkeys // nn                                              # (batch, diagonal flag): the launches keep their order
+    span = float(dens.max().item()) + 1.0
+    skey = cls.double() * (2.0 * span) + (span - dens if order_mode == "dense_first" else dens)
+    perm = torch.argsort(skey, stable=True)
+    if order_mode in TILE_ORDERS_EXPERIMENTAL:
+        perm = _experimental_tile_order(order_mode, perm, cls)
+    kc_p = kcounts[perm]
+    new_start = torch.empty_like(tile_start)
+    new_start[perm] = torch.cumsum(kc_p, 0) - kc_p
+    tile, upos = _entry_tile_index(tile_start, kcounts, total)
+    inv = torch.empty_like(tile)
+    inv[new_start[tile] + upos] = torch.arange(total, device=dev)
+    return A[inv], B[inv], tkeys[perm], kc_p
+
+
+def _group_patterns(A, B, seg_mask, bits, tile, upos, windows_per_tile, window):
+    """Stage 4a: inside windows of `window` consecutive entries of a tile, entries with the same pattern of 16-row blocks
+    (what the tile kernel can skip) are put next to each other: a quad's union is then the pattern of each of its four
+    entries.  Points with the same first camera end in different 16-row blocks of the last group and vice versa, so in plain
+    sweep order a quad ran 5.2 of 6 blocks per side where its entries own 4.85 (c3: 12 % of the matrix instructions)."""
+    nt = bits.shape[0]
+    pat = lambda m: (((m[:, None] & bits[None]) != 0).long() << torch.arange(nt, device=A.device)[None]).sum(1)
+    pkey = pat(seg_mask[A]) * (1 << nt) + pat(seg_mask[B])
+    order = torch.argsort((tile * windows_per_tile + upos // window) * (1 << (2 * nt)) + pkey, stable=True)
+    return A[order], B[order]
+
+
+def _quad_masks(emask, tile, upos, kcounts):
+    """Stage 4b: presence of a QUAD = union over its four entries (quads are aligned to the start of the tile, like the kernel's
+    batches), for every entry."""
+    total = emask.shape[0]
+    nquad = (kcounts + 3) // 4
+    quad = (torch.cumsum(nquad, 0) - nquad)[tile] + upos // 4
+    # (rows: an upper bound of the quad count that is known on the host -- sum ceil(k / 4) <= (total + 3 tiles) / 4 -- instead of
+    #  reading the sum back; the rows beyond the last quad are never gathered)
+    qm = torch.zeros(((total + 3 * int(kcounts.shape[0])) // 4 + 1, 4), dtype=torch.long, device=emask.device)
+    qm[quad, upos % 4] = emask
+    return (qm[:, 0] | qm[:, 1] | qm[:, 2] | qm[:, 3])[quad]
+
+
+def _cost_weighted_counts(kc, is_diag, tcost):
+    """Stage 5 (host): the entry count of every tile weighted by its cost per entry relative to the mean entry of its launch
+    kind.  Workgroups per tile are proportional to the tile's COST (_entry_cost), not to its entry count -- tiles whose points
+    see few of the 2 x 16 cameras skip most of their sub-tiles and ran 15 % ahead of the dense ones, the launch waiting for
+    the slowest (round 3 phase trace)."""
+    weight = np.ones_like(tcost)
+    for sel in (is_diag, ~is_diag):
+        if sel.any():
+            weight[sel] = (tcost[sel] / kc[sel]) / (tcost[sel].sum() / float(kc[sel].sum()))
+    return kc * weight
+
+
+def _size_chunks(kc, is_diag, tbatch, kw, chunk, max_chunks, merged_slots, nb, later_scale, top_up):
+    """Stage 6 (host, numpy): workgroups per tile for the cost-weighted entry counts kw.  kc, is_diag, tbatch: entries,
+    diagonal flag and batch of every tile."""
+    # (upper bound of a tile's workgroups: at least MIN_CHUNK entries each -- one sub-chunk at the very least)
+    nsub = np.maximum(np.minimum((kc + SUB - 1) // SUB, (kc + MIN_CHUNK - 1) // MIN_CHUNK), 1)
+    csize = np.full_like(kc, chunk)
+    topup = np.zeros_like(kc)
+    if max_chunks is not None:
+        # one resident round per launch: the smallest chunk size (multiple of SUB, >= MIN_CHUNK) whose workgroup
+        # count fits the device (CUs x workgroups per CU), so no workgroup starts late and runs alone on its CU
+        caps = max_chunks if isinstance(max_chunks, (tuple, list)) else (max_chunks, max_chunks)
+        if merged_slots is not None:
+            # ONE launch for both kinds of tiles (small problems): its resident slots are shared in proportion to the
+            # staged bytes (two segments per off-diagonal entry, one per diagonal entry)
+            e_off, e_diag = float(kc[~is_diag].sum()), float(kc[is_diag].sum())
+            n_off = int(round(merged_slots * 2.0 * e_off / max(2.0 * e_off + e_diag, 1.0)))
+            n_off = min(max(n_off, 1 if e_off else 0), merged_slots - (1 if e_diag else 0))
+            caps = (max(n_off, 1), max(merged_slots - n_off, 1))
+        for b in range(nb):
+            scale = 1.0 if b == 0 else later_scale
+            for sel, cap in ((~is_diag & (tbatch == b), int(caps[0] * scale)), (is_diag & (tbatch == b), int(caps[1] * scale))):
+                if not bool(sel.any()):
+                    continue
+                kcv, kwv, nsv = kc[sel], kw[sel], nsub[sel]
+                count = lambda c: np.minimum(np.maximum(np.ceil(kwv / (c * SUB)), 1.0).astype(np.int64), nsv)
+                lo, hi = MIN_CHUNK // SUB, max(MIN_CHUNK // SUB, int(-(-int(max(float(kwv.max()), float(kcv.max()))) // SUB)))
+                if int(count(hi).sum()) > cap:
+                    lo = hi                         # more tiles than slots: one workgroup per tile
+                while lo < hi:
+                    mid = (lo + hi) // 2
+                    lo, hi = (lo, mid) if int(count(mid).sum()) <= cap else (mid + 1, hi)
+                csize[sel] = lo * SUB
+                # top-up (round 5): the search stops at the first chunk size that fits, which leaves 1-3 % of the slots of
+                # a launch empty; they go, one by one, to the tile whose workgroups carry the most
+                n = count(lo)
+                spare = cap - int(n.sum())
+                if top_up and 0 < spare <= 64:
+                    for _ in range(spare):
+                        load = np.where(n < nsv, kwv / n.astype(np.float64), 0.0)
+                        i = int(np.argmax(load))
+                        if float(load[i]) <= 0.0:
+                            break
+                        n[i] += 1
+                    topup[sel] = n
+    nchunks = np.minimum(np.maximum(np.ceil(kw / csize.astype(np.float64)), 1.0).astype(np.int64), nsub)
+    return np.where(topup > 0, topup, nchunks)
+
+
+def _chunk_tables(kc, gI, gJ, is_diag, tbatch, nchunks, nb, ngroups):
+    """Stage 7 (host, numpy): chunk_desc, tile_desc and batch_desc (build_schur_tiles) from the per-tile tables in launch
+    order: workgroup j of a tile's J takes the sub-chunks j, j + J, ... of its entries."""
+    tile_start = np.cumsum(kc) - kc
+    cfirst = np.cumsum(nchunks) - nchunks
+    ctile = np.repeat(np.arange(kc.shape[0]), nchunks)                       # tile of every chunk
+    local = np.arange(ctile.shape[0]) - cfirst[ctile]
+    chunk_desc = np.stack([gI[ctile], gJ[ctile], tile_start[ctile], tile_start[ctile] + kc[ctile], local, nchunks[ctile]],
+                          1).astype(np.int32)
+    tile_desc = np.stack([gI, gJ, cfirst, cfirst + nchunks], 1).astype(np.int32)
+    batch_desc = np.zeros((nb, 6), dtype=np.int32)
+    for b in range(nb):
+        ids = np.nonzero(tbatch == b)[0]
+        if ids.size == 0:                           # (cannot happen for b = 0; later batches may be empty)
+            prev = int(batch_desc[b - 1, 2]) if b else 0
+            prevt = int(batch_desc[b - 1, 4]) if b else 0
+            batch_desc[b] = (prev, prev, prev, prevt, prevt, ngroups)
+            continue
+        c0 = int(cfirst[ids[0]])
+        c1 = int(cfirst[ids[-1]] + nchunks[ids[-1]])
+        dg = ids[is_diag[ids]]
+        cm = int(cfirst[dg[0]]) if dg.size else c1
+        batch_desc[b] = (c0, cm, c1, int(ids[0]), int(ids[-1]) + 1, int(gI[ids].min()))
+    return chunk_desc, tile_desc, batch_desc
+
+
 def build_schur_tiles(row_ptr, obs_cam, group=GROUP, chunk=CHUNK, max_chunks=None, num_batches=1, later_scale=1.0,
                       merged_slots=None, block_rows=6, simple=False, num_cams=None):
-    """Block-sparse Schur work list (device, torch ops; structure is fixed for the whole solve).
+    """Block-sparse Schur work list (structure is fixed for the whole solve).
 
     A *segment* is the run of one point's observations that falls into one group of `group`
     consecutive cameras; an *entry* pairs two segments (gI <= gJ) of the same point; entries are
@@ -255,292 +487,63 @@ def build_schur_tiles(row_ptr, obs_cam, group=GROUP, chunk=CHUNK, max_chunks=Non
     first_camera_group).  `later_scale` shrinks the workgroup caps of the batches after the first (they run on a
     CU-masked stream beside the factorisation).
 
-    Workgroups per tile: proportional to the tile's COST (_entry_cost: staging + the matrix instructions its presence masks
-    leave), not to its entry count -- tiles whose points see few of the 2 x 16 cameras skip most of their sub-tiles and ran
-    15 % ahead of the dense ones, the launch waiting for the slowest (round 3 phase trace); `block_rows` = rows per camera
-    of the tile blocks (6, or 6 + refined intrinsics when they are per camera).
+    Stages (the functions above): segments -> entry pairs sorted by tile and sweep position -> launch order of the tiles ->
+    pattern grouping and quad masks -> tile costs (_cost_weighted_counts; `block_rows` = rows per camera of the tile blocks, 6,
+    or 6 + refined intrinsics when they are per camera) -> chunk sizing -> the chunk, tile and batch tables.  The entry list is
+    built with torch ops on the device of `obs_cam`; the per-tile tables go to the host in one copy and the last two stages
+    run there.
 
     `merged_slots`: the off-diagonal and the diagonal chunks will run in ONE launch (vgg_ba_problem.merged_tile_launch) with
     that many resident workgroups in all; the split between the two kinds follows their entry counts.
 
     `simple` (round 6; compile_problem sets it below SIMPLE_WORKLIST_MAX_OBS observations -- video windows): the launch of a
-    small problem takes ~30 us whatever its schedule, while this function is ~400 torch launches and ~35 host reads; the simple
-    list keeps the (gI, gJ) tile order and the plain sweep order inside a tile, hands out workgroups by entry count and reads
-    the per-tile tables back in one copy each.  Same tiles, same entries per tile, same sums up to their order.
+    small problem takes ~30 us whatever its schedule, while the full list costs hundreds of torch launches; the simple list
+    keeps the (gI, gJ) tile order and the plain sweep order inside a tile and hands out workgroups by entry count.  Same
+    tiles, same entries per tile, same sums up to their order.
     `num_cams`: the number of cameras (saves the two host reads that derive it from `obs_cam`)."""
     dev = obs_cam.device
-    O = obs_cam.shape[0]
-    P = row_ptr.shape[0] - 1
-    if O == 0:
+    if obs_cam.shape[0] == 0:
         z = torch.zeros((0, 4), dtype=torch.int32, device=dev)
         return (torch.zeros((0, 6), dtype=torch.int32, device=dev), z, z.clone(), torch.zeros(0, dtype=torch.int32, device=dev), 0,
                 torch.zeros((1, 6), dtype=torch.int32))
-    counts = (row_ptr[1:] - row_ptr[:-1]).long()
-    obs_pt = torch.repeat_interleave(torch.arange(P, device=dev), counts, output_size=O)   # (output_size: no host read inside)
-    grp = (obs_cam // group).long()
-    is_start = torch.ones(O, dtype=torch.bool, device=dev)
-    is_start[1:] = (obs_pt[1:] != obs_pt[:-1]) | (grp[1:] != grp[:-1])
-    seg_begin = torch.nonzero(is_start).squeeze(1)
-    nseg = seg_begin.shape[0]
-    seg_id = torch.cumsum(is_start.long(), 0) - 1
-    # presence mask of the segment: bit l <=> camera group*16 + l observes the point
-    seg_mask = torch.zeros(nseg, dtype=torch.long, device=dev).index_add_(0, seg_id, 1 << (obs_cam.long() % group))
-    seg_pt = obs_pt[seg_begin]
-    seg_grp = grp[seg_begin]
     ncam = int(num_cams) if num_cams is not None else int(obs_cam.max().item()) + 1
     ngroups = (ncam - 1) // group + 1
-    pseg_ptr = torch.zeros(P + 1, dtype=torch.long, device=dev)
-    pseg_ptr[1:] = torch.cumsum(torch.bincount(seg_pt, minlength=P), 0)
-    idx = torch.arange(nseg, device=dev)
-    npair = pseg_ptr[seg_pt + 1] - idx
-    total = int(npair.sum().item())
-    A = torch.repeat_interleave(idx, npair, output_size=total)
-    pair_start = torch.cumsum(npair, 0) - npair
-    B = A + (torch.arange(total, device=dev) - pair_start[A])
-    # batch of a camera group: runs of consecutive groups gI with about equal numbers of entries
-    gA, gB = seg_grp[A], seg_grp[B]
-    # sweep position of a point: all tiles walk the points in the order (first camera, last camera), so that the four
-    # entries a workgroup packs along K (a "quad") have about the same presence pattern (the tile kernels skip the 16-row
-    # blocks in which none of the four has a camera) and every tile still meets a given point at about the same time
-    has = counts > 0
-    first_cam = torch.where(has, obs_cam.long()[row_ptr[:-1].long().clamp(max=O - 1)], torch.zeros_like(counts))
-    last_cam = torch.where(has, obs_cam.long()[(row_ptr[1:].long() - 1).clamp(min=0)], torch.zeros_like(counts))
-    prank = torch.empty(P, dtype=torch.long, device=dev)
-    prank[torch.argsort(first_cam * ncam + last_cam, stable=True)] = torch.arange(P, device=dev)
-    nb = max(1, min(int(num_batches), ngroups))
-    if nb == 1:                                                     # (one batch: no counts, no host read)
-        batch_of_group = torch.zeros(ngroups, dtype=torch.long, device=dev)
-    else:
-        per_group = torch.bincount(gA, minlength=ngroups).double()
-        cum = torch.cumsum(per_group, 0) - per_group                # entries before group g
-        batch_of_group = torch.clamp((cum * nb / max(float(total), 1.0)).long(), max=nb - 1)   # (per_group.sum() = total)
-        batch_of_group = torch.cummax(batch_of_group, 0).values
-    # tile key: batch-major; inside a batch the off-diagonal tiles first, then the diagonal ones (separate launches)
     nn = ngroups * ngroups
-    key = batch_of_group[gA] * (2 * nn) + (gA == gB).long() * nn + gA * ngroups + gB
-    epos = prank[seg_pt[A]]
-    order = torch.argsort(key * P + epos)
-    A, B, key, epos = A[order], B[order], key[order], epos[order]
-    emask = seg_mask[A] | (seg_mask[B] << 16)
-    ukeys, kcounts = torch.unique_consecutive(key, return_counts=True)              # chunking unit = tile
-    tile_start = torch.cumsum(kcounts, 0) - kcounts
+    nb = max(1, min(int(num_batches), ngroups))
     order_mode = "plain" if simple else _hook("VGGSFM_TILE_ORDER", TILE_ORDER)
     if order_mode not in TILE_ORDERS + TILE_ORDERS_EXPERIMENTAL:
         raise ValueError(f"tile order {order_mode!r}: expected one of {TILE_ORDERS + TILE_ORDERS_EXPERIMENTAL}")
-    if order_mode != "plain" and nb == 1 and ukeys.shape[0] > 2:
-        # LAUNCH ORDER of the tiles by density (round 5): the workgroups of a launch are resident three (four) to a CU --
-        # positions p, p + CUs, p + 2 CUs -- and the oldest is served first; in (gI, gJ) order neighbouring positions hold
-        # tiles of like density.  Ordered by the mean number of 16-row block products of their entries (own patterns), the
-        # launch walks from the sparsest tiles to the densest and every CU gets a mix.  Same-box A/B at configs[2]
-        # (profiles/r05_ab_tile_order_c3.jsonl): densest first 0.564 / 0.247 ms (off-diagonal / diagonal launch), (gI, gJ)
-        # order 0.542 / 0.252, SPARSEST FIRST 0.536 / 0.243 -- the default; densities scattered over the launch 0.570 /
-        # 0.244.  The sums of a tile do not depend on where it is launched (final costs equal to the last bit).
-        # (per-tile sums of a list sorted by tile = differences of a running sum; the runs are then moved as blocks -- no
-        #  second sort and no atomics: an index_add_ of 6 M doubles into ~100 bins takes seconds)
-        nt_ = block_rows * group // 16
-        bits_ = torch.tensor([(((2 << min(group - 1, (16 * b + 15) // block_rows)) - 1) & ~((1 << ((16 * b) // block_rows)) - 1))
-                              for b in range(nt_)], dtype=torch.long, device=dev)
-        nblk = lambda m: ((m[:, None] & bits_[None]) != 0).sum(1)
-        csum_d = torch.cumsum((nblk(seg_mask[A]) * nblk(seg_mask[B])).double(), 0)
-        tend_d = tile_start + kcounts - 1
-        dsum = csum_d[tend_d] - torch.where(tile_start > 0, csum_d[(tile_start - 1).clamp(min=0)], torch.zeros_like(csum_d[tend_d]))
-        dens = dsum / kcounts.double()
-        cls = ukeys // nn                                              # (batch, diagonal flag): the launches keep their order
-        span = float(dens.max().item()) + 1.0
-        skey = cls.double() * (2.0 * span) + (span - dens if order_mode == "dense_first" else dens)
-        perm_units = torch.argsort(skey, stable=True)
-        if order_mode == "stride":                                       # (experiment: densities scattered over a launch)
-            ncls = torch.bincount(cls)
-            cstart = torch.cumsum(ncls, 0) - ncls
-            r = torch.arange(perm_units.shape[0], device=dev) - cstart[cls[perm_units]]
-            nc = ncls[cls[perm_units]]
-            step = torch.clamp((nc.double().sqrt().long() | 1), min=1)
-            while bool((torch.gcd(step, nc) != 1).any()):
-                step = torch.where(torch.gcd(step, nc) != 1, step + 2, step)
-            newr = (r * step) % nc
-            perm_units = perm_units[torch.argsort(cstart[cls[perm_units]] + newr, stable=True)]
-        if order_mode in ("sdm", "msd", "dsm"):                          # (experiment: the density thirds of a launch in another order)
-            ncls = torch.bincount(cls)
-            cstart = torch.cumsum(ncls, 0) - ncls
-            cp = cls[perm_units]
-            r = torch.arange(perm_units.shape[0], device=dev) - cstart[cp]
-            third = torch.clamp((3 * r) // ncls[cp].clamp(min=1), max=2)       # 0 sparse, 1 mid, 2 dense
-            slot = {"sdm": (0, 2, 1), "msd": (1, 0, 2), "dsm": (2, 0, 1)}[order_mode]
-            where = torch.tensor([slot.index(t) for t in range(3)], device=dev)[third]
-            perm_units = perm_units[torch.argsort(cp * 4 + where, stable=True)]
-        new_start = torch.empty_like(tile_start)
-        kc_p = kcounts[perm_units]
-        new_start[perm_units] = torch.cumsum(kc_p, 0) - kc_p
-        unit0 = torch.repeat_interleave(torch.arange(kcounts.shape[0], device=dev), kcounts, output_size=total)
-        dest = new_start[unit0] + (torch.arange(total, device=dev) - tile_start[unit0])
-        inv = torch.empty_like(dest)
-        inv[dest] = torch.arange(total, device=dev)
-        A, B, key, epos, emask = A[inv], B[inv], key[inv], epos[inv], emask[inv]
-        ukeys, kcounts = ukeys[perm_units], kc_p
-        tile_start = torch.cumsum(kcounts, 0) - kcounts
     quad_window = 0 if simple else int(_hook("VGGSFM_QUAD_SORT_WINDOW", QUAD_SORT_WINDOW))
     top_up = (not simple) and _hook("VGGSFM_TILE_TOP_UP", "1" if TILE_TOP_UP else "0") != "0"
+
+    seg_pt, seg_grp, seg_mask, obs_slot = _segments(row_ptr, obs_cam, group)
+    A, B, tkeys, kcounts = _entry_pairs(seg_pt, seg_grp, _sweep_rank(row_ptr, obs_cam, ncam), ngroups, nb)
+    bits = None if simple else torch.tensor(_block_slot_bits(block_rows, group), dtype=torch.long, device=dev)
+    if order_mode != "plain" and nb == 1 and tkeys.shape[0] > 2:
+        A, B, tkeys, kcounts = _launch_order(order_mode, A, B, tkeys, kcounts, seg_mask, bits, nn)
+    tile_start = torch.cumsum(kcounts, 0) - kcounts
+    tile, upos = _entry_tile_index(tile_start, kcounts, A.shape[0])
     if quad_window > 0:
-        # Inside windows of QUAD_SORT_WINDOW consecutive entries of a tile, entries with the same pattern of 16-row blocks
-        # (what the tile kernel can skip) are put next to each other: a quad's union is then the pattern of each of its four
-        # entries.  Points with the same first camera end in different 16-row blocks of the last group and vice versa, so in
-        # plain sweep order a quad ran 5.2 of 6 blocks per side where its entries own 4.85 (c3: 12 % of the matrix instructions).
-        nt = block_rows * group // 16
-        bits = [(((2 << min(group - 1, (16 * b + 15) // block_rows)) - 1) & ~((1 << ((16 * b) // block_rows)) - 1)) for b in range(nt)]
-        bits_t = torch.tensor(bits, dtype=torch.long, device=dev)
-        pat = lambda m: (((m[:, None] & bits_t[None]) != 0).long() << torch.arange(nt, device=dev)[None]).sum(1)
-        pkey = pat(seg_mask[A]) * (1 << nt) + pat(seg_mask[B])
-        unit0 = torch.repeat_interleave(torch.arange(kcounts.shape[0], device=dev), kcounts, output_size=total)
-        upos0 = torch.arange(total, device=dev) - tile_start[unit0]
-        wkey = (unit0 * (int(kcounts.max().item()) // quad_window + 1) + upos0 // quad_window) * (1 << (2 * nt)) + pkey
-        order2 = torch.argsort(wkey, stable=True)
-        A, B, epos, emask = A[order2], B[order2], epos[order2], emask[order2]
-    # presence of a quad = union over its four entries (quads are aligned to the start of the unit, like the kernel's batches)
-    unit_of_entry = torch.repeat_interleave(torch.arange(kcounts.shape[0], device=dev), kcounts, output_size=total)
-    upos = torch.arange(total, device=dev) - tile_start[unit_of_entry]
-    nquad = (kcounts + 3) // 4
-    quad = (torch.cumsum(nquad, 0) - nquad)[unit_of_entry] + upos // 4
-    # (rows: an upper bound of the quad count that is known on the host -- sum ceil(k / 4) <= (total + 3 units) / 4 -- instead of
-    #  reading the sum back; the rows beyond the last quad are never gathered)
-    qm = torch.zeros(((total + 3 * int(kcounts.shape[0])) // 4 + 1, 4), dtype=torch.long, device=dev)
-    qm[quad, upos % 4] = emask
-    qm = qm[:, 0] | qm[:, 1] | qm[:, 2] | qm[:, 3]
+        A, B = _group_patterns(A, B, seg_mask, bits, tile, upos, int(kcounts.max().item()) // quad_window + 1, quad_window)
+    qmask = _quad_masks(seg_mask[A] | (seg_mask[B] << 16), tile, upos, kcounts)
     # (field 0 = the entry's POINT, row of `pts`: the diagonal tile launch fetches the point's back-substitution block by it --
     #  vgg_ba_set_tile_rhs; the sweep position only orders the list)
-    entries = torch.stack([seg_pt[A], A, B, qm[quad]], 1).to(torch.int32)
-    tbatch = ukeys // (2 * nn)
-    is_diag = (ukeys % (2 * nn)) >= nn
-    ukeys = ukeys % nn
-    if simple:
-        kw = kcounts.double()                               # workgroups by entry count
-    else:
-        # cost-weighted entry count of every tile (relative to the mean entry of its launch kind)
-        ecost = _entry_cost(qm[quad], is_diag[unit_of_entry], block_rows, group)
-        # (per-tile sums of a list that is sorted by tile: differences of a running sum -- index_add_ with 5 M double atomics
-        #  cost 2.4 ms of a 10 ms compile at configs[2])
-        csum = torch.cumsum(ecost, 0)
-        tend = tile_start + kcounts - 1
-        tcost = csum[tend] - torch.where(tile_start > 0, csum[(tile_start - 1).clamp(min=0)], torch.zeros_like(csum[tend]))
-        kweight = torch.ones_like(tcost)
-        for sel in (is_diag, ~is_diag):
-            if bool(sel.any()):
-                kweight[sel] = (tcost[sel] / kcounts[sel].double()) / (tcost[sel].sum() / kcounts[sel].sum().double())
-        kw = kcounts.double() * kweight
-    # (upper bound of a tile's workgroups: at least MIN_CHUNK entries each -- one sub-chunk at the very least)
-    nsub_t = torch.clamp(torch.minimum((kcounts + SUB - 1) // SUB, (kcounts + MIN_CHUNK - 1) // MIN_CHUNK), min=1)
-
-    def size_chunks(kw):
-        """workgroups per tile for the cost-weighted entry counts kw"""
-        csize = torch.full_like(kcounts, chunk)
-        if max_chunks is not None:
-            # one resident round per launch: the smallest chunk size (multiple of SUB, >= MIN_CHUNK) whose workgroup
-            # count fits the device (CUs x workgroups per CU), so no workgroup starts late and runs alone on its CU
-            caps = max_chunks if isinstance(max_chunks, (tuple, list)) else (max_chunks, max_chunks)
-            if merged_slots is not None:
-                # ONE launch for both kinds of tiles (small problems): its resident slots are shared in proportion to the
-                # staged bytes (two segments per off-diagonal entry, one per diagonal entry)
-                kc0, dg0 = ht[0].astype(np.int64), ht[1] != 0
-                e_off, e_diag = float(kc0[~dg0].sum()), float(kc0[dg0].sum())
-                n_off = int(round(merged_slots * 2.0 * e_off / max(2.0 * e_off + e_diag, 1.0)))
-                n_off = min(max(n_off, 1 if e_off else 0), merged_slots - (1 if e_diag else 0))
-                caps = (max(n_off, 1), max(merged_slots - n_off, 1))
-            # (the search runs on host copies of the per-tile counts: one synchronisation instead of one per probe -- and, since
-            #  round 6, in numpy: a dozen probes of a handful of tiny torch CPU tensors cost 0.4 ms of a 2.9 ms window compile)
-            kc_h, diag_h, tb_h, ns_h = ht[0].astype(np.int64), ht[1] != 0, ht[2].astype(np.int64), ht[3].astype(np.int64)
-            kw_h = kw.cpu().numpy() if kw is not kw_first else ht[4]
-            csize_h = np.full_like(kc_h, chunk)
-            topup_h = np.zeros_like(kc_h)
-            for b in range(nb):
-                scale = 1.0 if b == 0 else later_scale
-                for sel, cap in ((~diag_h & (tb_h == b), int(caps[0] * scale)), (diag_h & (tb_h == b), int(caps[1] * scale))):
-                    if not bool(sel.any()):
-                        continue
-                    kc, kwv, nsv = kc_h[sel], kw_h[sel], ns_h[sel]
-                    lo, hi = MIN_CHUNK // SUB, max(MIN_CHUNK // SUB, int(-(-int(max(float(kwv.max()), float(kc.max()))) // SUB)))
-                    fits = lambda c: int(np.minimum(np.maximum(np.ceil(kwv / (c * SUB)), 1.0).astype(np.int64), nsv).sum()) <= cap
-                    if not fits(hi):
-                        lo = hi                         # more tiles than slots: one workgroup per tile
-                    while lo < hi:
-                        mid = (lo + hi) // 2
-                        lo, hi = (lo, mid) if fits(mid) else (mid + 1, hi)
-                    csize_h[sel] = lo * SUB
-                    # top-up (round 5): the search stops at the first chunk size that fits, which leaves 1-3 % of the slots of
-                    # a launch empty; they go, one by one, to the tile whose workgroups carry the most
-                    n_h = np.minimum(np.maximum(np.ceil(kwv / (lo * SUB)), 1.0).astype(np.int64), nsv)
-                    spare = cap - int(n_h.sum())
-                    if top_up and 0 < spare <= 64:
-                        for _ in range(spare):
-                            load = np.where(n_h < nsv, kwv / n_h.astype(np.float64), 0.0)
-                            i = int(np.argmax(load))
-                            if float(load[i]) <= 0.0:
-                                break
-                            n_h[i] += 1
-                        topup_h[sel] = n_h
-            csize = torch.from_numpy(csize_h).to(dev)
-        nchunks = torch.minimum(torch.clamp(torch.ceil(kw / csize.double()), min=1).long(), nsub_t)
-        if max_chunks is not None and bool((topup_h > 0).any()):
-            th = torch.from_numpy(topup_h).to(dev)
-            nchunks = torch.where(th > 0, th, nchunks)
-        return nchunks
-
-    # (the per-tile tables the search reads: ONE copy to the host -- they are exact in float64)
-    kw_first = kw
-    host_tables = torch.stack([kcounts.double(), is_diag.double(), tbatch.double(), nsub_t.double(), kw]).cpu()
-    ht = host_tables.numpy()
-    nchunks = size_chunks(kw)
-    # POSITION weight (round 5): the workgroups of a launch are all resident at once, three (four) to a CU, and the SIMDs
-    # arbitrate oldest-first -- the workgroup that was dispatched LAST onto a CU gets the issue slots its elders leave.  Per-tile
-    # phase trace at configs[2] (scripts/prof/tile_cost_fit.py): 4450 cycles per batch in the first third of the launch, 4800
-    # in the second, 5180 in the third, for the same matrix instructions per batch.  So a tile's cost grows with the position
-    # of its workgroups in the launch: second pass with kw (1 + TILE_POSITION_WEIGHT x position fraction within its launch).
-    pw = 0.0 if simple else float(_hook("VGGSFM_TILE_POS_WEIGHT", TILE_POSITION_WEIGHT))
-    if pw != 0.0 and max_chunks is not None and kcounts.shape[0] > 1:
-        launch_key = tbatch * 2 + is_diag.long()                   # (units are sorted by batch, off-diagonal first)
-        cum = torch.cumsum(nchunks, 0).double()
-        total_of = torch.zeros(int(launch_key.max().item()) + 1, dtype=torch.float64, device=dev).index_add_(0, launch_key, nchunks.double())
-        starts = torch.cumsum(total_of, 0) - total_of
-        frac = ((cum - 0.5 * nchunks.double()) - starts[launch_key]) / total_of[launch_key].clamp(min=1.0)
-        nchunks = size_chunks(kw * (1.0 + pw * frac))
-    ctile = torch.repeat_interleave(torch.arange(ukeys.shape[0], device=dev), nchunks)          # unit of every chunk
-    cfirst = torch.cumsum(nchunks, 0) - nchunks
-    local = torch.arange(ctile.shape[0], device=dev) - cfirst[ctile]
-    chunk_desc = torch.stack([ukeys[ctile] // ngroups, ukeys[ctile] % ngroups, tile_start[ctile],
-                              tile_start[ctile] + kcounts[ctile], local, nchunks[ctile]], 1).to(torch.int32)
-    # tiles: runs of consecutive units with the same tile key (the partial tiles of ALL their chunks are summed)
-    ukey_full = tbatch * (2 * nn) + is_diag.long() * nn + ukeys
-    new_tile = torch.ones_like(ukey_full, dtype=torch.bool)
-    new_tile[1:] = ukey_full[1:] != ukey_full[:-1]
-    tfirst_unit = torch.nonzero(new_tile).squeeze(1)
-    tile_of_unit = torch.cumsum(new_tile.long(), 0) - 1
-    t_chunks = torch.zeros(tfirst_unit.shape[0], dtype=torch.long, device=dev).index_add_(0, tile_of_unit, nchunks)
-    t_cfirst = cfirst[tfirst_unit]
-    tile_desc = torch.stack([ukeys[tfirst_unit] // ngroups, ukeys[tfirst_unit] % ngroups, t_cfirst, t_cfirst + t_chunks],
-                            1).to(torch.int32)
-    obs_slot = (seg_id * group + obs_cam.long() % group).to(torch.int32)
-    # host-side batch table (per tile)
-    tbatch, is_diag, ukeys = tbatch[tfirst_unit], is_diag[tfirst_unit], ukeys[tfirst_unit]
-    tt = torch.stack([tbatch, is_diag.long(), t_chunks, t_cfirst, ukeys // ngroups]).cpu().numpy()      # (one copy)
-    tb, td, tn, tf, tg = tt[0], tt[1] != 0, tt[2], tt[3], tt[4]
-    bd = np.zeros((nb, 6), dtype=np.int32)
-    for b in range(nb):
-        ids = np.nonzero(tb == b)[0]
-        if ids.size == 0:                           # (cannot happen for b = 0; later batches may be empty)
-            prev = int(bd[b - 1, 2]) if b else 0
-            prevt = int(bd[b - 1, 4]) if b else 0
-            bd[b] = (prev, prev, prev, prevt, prevt, ngroups)
-            continue
-        c0 = int(tf[ids[0]])
-        c1 = int(tf[ids[-1]] + tn[ids[-1]])
-        dg = ids[td[ids]]
-        cm = int(tf[dg[0]]) if dg.size else c1
-        bd[b] = (c0, cm, c1, int(ids[0]), int(ids[-1]) + 1, int(tg[ids].min()))
-    batch_desc = torch.from_numpy(bd)
-    return (chunk_desc.contiguous(), entries.contiguous(), tile_desc.contiguous(), obs_slot.contiguous(), int(nseg),
-            batch_desc.contiguous())
+    entries = torch.stack([seg_pt[A], A, B, qmask], 1).to(torch.int32)
+    # the per-tile tables: ONE copy to the host (they are exact in float64)
+    rows = [kcounts.double(), tkeys.double()]
+    if not simple:
+        rows.append(_tile_sums(_entry_cost(qmask, ((tkeys % (2 * nn)) >= nn)[tile], block_rows, group), tile_start, kcounts))
+    ht = torch.stack(rows).cpu().numpy()
+    kc, tk = ht[0].astype(np.int64), ht[1].astype(np.int64)
+    tbatch, is_diag, tk = tk // (2 * nn), (tk % (2 * nn)) >= nn, tk % nn
+    kw = ht[0] if simple else _cost_weighted_counts(kc, is_diag, ht[2])             # (simple: workgroups by entry count)
+    nchunks = _size_chunks(kc, is_diag, tbatch, kw, chunk, max_chunks, merged_slots, nb, later_scale, top_up)
+    chunk_desc, tile_desc, batch_desc = _chunk_tables(kc, tk // ngroups, tk % ngroups, is_diag, tbatch, nchunks, nb, ngroups)
+    return (torch.from_numpy(chunk_desc).to(dev), entries.contiguous(), torch.from_numpy(tile_desc).to(dev), obs_slot.contiguous(),
+            int(seg_pt.shape[0]), torch.from_numpy(batch_desc))
 
 
 SORT_POINTS = True                 # bundle_adjustment: number the problem's points by track length (compile_problem); hook VGGSFM_SORT_POINTS=0
-TILE_BACKFILL = None               # (off-diagonal, diagonal) workgroups per CU of the single back-filled tile launch; None = two launches
 TILE_WGS_PER_CU = (3, 4)           # resident schur_tile workgroups per CU with 6 x 6 blocks: (off-diagonal, diagonal) launch
 SPARSE_GRID_DENSITY = 0.05        # compile_problem: below this fill of the (frames x tracks) grid work on the observation list
 MERGED_TILE_MAX_OBS = 1_000_000   # below: off-diagonal and diagonal tiles share one launch
@@ -842,18 +845,6 @@ def compile_problem(points3d, extrinsics, intrinsics, tracks, masks, extra_param
     # small problems: one tile launch (c2, 0.25 M observations: 0.101 -> 0.068 ms for the tiles; c3, 5 M: 0.84 -> 0.90 ms)
     merged = nb == 1 and int(obs_cam.shape[0]) < MERGED_TILE_MAX_OBS
     merged_slots = slots[0] if merged else None
-    backfill = TILE_BACKFILL if block_rows == 6 else None
-    if _hook("VGGSFM_TILE_BACKFILL"):                  # measurement hook: "off,diag" workgroups per CU, or "0" = two launches
-        v = _hook("VGGSFM_TILE_BACKFILL")
-        backfill = None if v == "0" else tuple(float(x) for x in v.split(","))
-    if backfill is not None and nb == 1 and not merged:
-        # ONE launch, off-diagonal chunks first (one resident round at the merged kernel's occupancy), the diagonal chunks
-        # behind them: the in-order dispatcher hands a diagonal workgroup to every slot an off-diagonal one leaves, so the
-        # ~16 % of the chip that idled while the slowest off-diagonal tiles finished (round 3 phase trace) computes diagonal
-        # tiles instead.  (Not the round-2 "merged" form, where both kinds shared one resident round and swept the points
-        # together: 0.90 ms against 0.62 + 0.24.)
-        merged, merged_slots = True, None
-        slots = (max(1, int(cus * backfill[0])), max(1, int(cus * backfill[1])))
     chunk_desc, entries, tile_desc, obs_slot, nseg, batch_desc = build_schur_tiles(
         row_ptr, obs_cam, max_chunks=slots, num_batches=nb, later_scale=(cus - CHOL_CUS) / cus,
         merged_slots=merged_slots, block_rows=block_rows, simple=int(obs_cam.shape[0]) < SIMPLE_WORKLIST_MAX_OBS, num_cams=S)
@@ -904,13 +895,12 @@ def _summary_dict(summ, log, n):
 
 
 def apply_launch_hooks(L):
-    """Measurement hooks of a solve (solve, dist.ShardedBA.begin): VGGSFM_LEGACY_GLUE "1" = the separate glue launches, "0" =
-    the merged ones; VGGSFM_LEGACY_STEP "1" = point_step's sweep over full Jacobians, "0" = the directional one.  Either
-    variable, with either value, also sets the right-hand-side mode to 2 (the default): vgg_ba_set_tile_rhs takes all of them in
-    one integer and has no getter, so a harness that chose mode 0 / 1 must set neither (scripts/prof/ab_c3.py does not)."""
-    glue, step = _hook("VGGSFM_LEGACY_GLUE"), _hook("VGGSFM_LEGACY_STEP")
-    if glue is not None or step is not None:
-        L.vgg_ba_set_tile_rhs(2 | (4 if glue == "1" else 0) | (8 if step == "1" else 0))
+    """Measurement hook of a solve (solve, dist.ShardedBA.begin): VGGSFM_LEGACY_GLUE "1" = the separate glue launches, "0" = the
+    merged ones.  Either value also sets the right-hand-side mode to 2 (the default): vgg_ba_set_tile_rhs takes both in one
+    integer and has no getter, so a harness that chose mode 0 / 1 must not set the variable (scripts/prof/ab_c3.py does not)."""
+    glue = _hook("VGGSFM_LEGACY_GLUE")
+    if glue is not None:
+        L.vgg_ba_set_tile_rhs(2 | (4 if glue == "1" else 0))
 
 
 def solve(problem: DeviceProblem, options: Optional[BundleAdjustmentOptions] = None, workspace=None):

@@ -174,10 +174,8 @@ static Dims make_dims(const vgg_ba_problem* pb) {
 // overrides of the automatic launch choices (vgg_ba_tuning, vgg_ba_set_tile_rhs): 0 / -1 = automatic
 // legacy_glue (vgg_ba_set_tile_rhs(| 4), A/B runs and tests): tile sums, assembly, preparation and the step sums as the separate
 // launches they were before they were merged (tile_assemble_kernel, cam_reduce_kernel's last arriver)
-// legacy_step (vgg_ba_set_tile_rhs(| 8), A/B runs): point_step's sweep over full Jacobians with the model cost change summed
-// observation by observation, as before the directional sweep
-struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs, legacy_glue, legacy_step; };
-static Tuning g_tuning = {0, -1, 0, 0, 2, 0, 0};
+struct Tuning { int lpp, longt, cam_wgs, point_wgs, tile_rhs, legacy_glue; };
+static Tuning g_tuning = {0, -1, 0, 0, 2, 0};
 
 static Ws carve(const Dims& d, int max_iters, int num_chunks, int num_segments, void* base) {
   Ws w;
@@ -2286,7 +2284,7 @@ __global__ __launch_bounds__(256) void tile_assemble_kernel(DevProblem pb, Ws w,
 // several ranks all-reduced, so the share is the same on every rank and control_kernel adds it un-reduced).  A shared
 // intrinsics block enters through every camera's BD x BD block.
 template <int KD>
-__device__ __forceinline__ void cam_update_body(const DevProblem& pb, const Ws& w, int c, bool cam_mcc) {
+__device__ __forceinline__ void cam_update_body(const DevProblem& pb, const Ws& w, int c) {
   constexpr int BD = 6 + KD;
   const Dims& d = pb.d;
   double step = 0, xn = 0, mcc = 0;
@@ -2308,25 +2306,23 @@ __device__ __forceinline__ void cam_update_body(const DevProblem& pb, const Ws& 
     for (int k = 0; k < 4; ++k) { w.cand_q[4 * c + k] = qn[k]; const double df = qn[k] - pb.cam_q[4 * c + k]; step += df * df; if (pose_var) xn += pb.cam_q[4 * c + k] * pb.cam_q[4 * c + k]; }
 #pragma unroll
     for (int k = 0; k < 3; ++k) { const double tn = pb.cam_t[3 * c + k] + dl[3 + k]; w.cand_t[3 * c + k] = tn; step += dl[3 + k] * dl[3 + k]; if (pose_var) xn += pb.cam_t[3 * c + k] * pb.cam_t[3 * c + k]; }
-    if (cam_mcc) {
 #pragma unroll
-      for (int k = 0; k < KD; ++k) {
-        const int j = 6 * d.C + KD * (d.shared ? 0 : c) + k;
-        dyc[6 + k] = w.active[j] ? w.scale_c[j] * w.rhs[j] : 0.0;
-      }
-      const double* U = w.U + (size_t)c * BD * BD;
-      const double* g = w.g + (size_t)c * BD;
-      double lin = 0, quad = 0;
-#pragma unroll
-      for (int i = 0; i < BD; ++i) {
-        double ud = 0;
-#pragma unroll
-        for (int k = 0; k < BD; ++k) ud += U[i * BD + k] * dyc[k];
-        lin += dyc[i] * g[i];
-        quad += dyc[i] * ud;
-      }
-      mcc = lin - 0.5 * quad;
+    for (int k = 0; k < KD; ++k) {
+      const int j = 6 * d.C + KD * (d.shared ? 0 : c) + k;
+      dyc[6 + k] = w.active[j] ? w.scale_c[j] * w.rhs[j] : 0.0;
     }
+    const double* U = w.U + (size_t)c * BD * BD;
+    const double* g = w.g + (size_t)c * BD;
+    double lin = 0, quad = 0;
+#pragma unroll
+    for (int i = 0; i < BD; ++i) {
+      double ud = 0;
+#pragma unroll
+      for (int k = 0; k < BD; ++k) ud += U[i * BD + k] * dyc[k];
+      lin += dyc[i] * g[i];
+      quad += dyc[i] * ud;
+    }
+    mcc = lin - 0.5 * quad;
   }
   // intrinsics block a == c (per camera) or block 0 handled by the extra thread c == C (shared)
   const int a = d.shared ? ((c == d.C) ? 0 : -1) : ((c < d.C) ? c : -1);
@@ -2350,7 +2346,6 @@ __device__ __forceinline__ void cam_update_body(const DevProblem& pb, const Ws& 
 #pragma unroll
     for (int k = 0; k < 4; ++k) { w.cand_intr[4 * a + k] = in4[k]; if (intr_var && k < np) xn += pb.intr[4 * a + k] * pb.intr[4 * a + k]; }
   }
-  // (cam_mcc off: point_step_kernel<.., DIR = false> sums the cameras' share observation by observation)
   w.cam_part[3 * c] = step;
   w.cam_part[3 * c + 1] = xn;
   w.cam_part[3 * c + 2] = mcc;
@@ -2359,11 +2354,11 @@ __device__ __forceinline__ void cam_update_body(const DevProblem& pb, const Ws& 
 // (a launch of its own where point_step_kernel does not run the body in its prologue: a camera table over 64 KB, the
 //  separate glue launches)
 template <int KD>
-__global__ void cam_update_kernel(DevProblem pb, Ws w, int cam_mcc) {
+__global__ void cam_update_kernel(DevProblem pb, Ws w) {
   if (w.ctl->done) return;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c > pb.d.C) return;
-  cam_update_body<KD>(pb, w, c, cam_mcc != 0);
+  cam_update_body<KD>(pb, w, c);
 }
 
 // back-substitution, model cost change and candidate point: LPP lanes per point (see point_pass_kernel).  The candidate's
@@ -2371,25 +2366,24 @@ __global__ void cam_update_kernel(DevProblem pb, Ws w, int cam_mcc) {
 // its cost decides the step.  (A second sweep here used to evaluate the same residuals for the cost alone, and after an
 // accepted step cam_pass<LIN> evaluated them once more; c3: this launch 0.101 -> 0.079 ms without that sweep.)
 //
-// DIR: the sweep in directional form.  What it needs of an observation is fy = F dy_c -- ONE directional derivative along the
+// The sweep is in directional form.  What it needs of an observation is fy = F dy_c -- ONE directional derivative along the
 // camera's step -- and the adjoint product E^T fy = R^T JY^T fy, so neither the 2 x BD block F nor the 2 x 3 block E is built
 // (obs_step_R, camera_model.hpp).  dy is zero in every inactive column (cam_update_body; init_kernel derives `active` from
 // cam_const / intr_const exactly as eval_full masks F), so the constant-parameter masks of F drop out; a constant point
 // contributes nothing, as E = 0 did.  The cameras' share of the model cost change comes from cam_update_body, camera by
 // camera from U | g, so under the trivial loss the sweep needs no residual at all.  Robust loss (kernel-uniform branch):
 // the corrector C = sqrt(rho') (I - alpha r r^T) multiplies both Jacobians from the left, fy' = C fy and E'^T fy' = E^T C fy'.
-// DIR = false (vgg_ba_set_tile_rhs(| 8)) is the sweep over full Jacobians it replaced, for A/B runs in one library.
+// (The sweep over full Jacobians it replaced: tests/test_gpu_ba_step_sweep.py, profiles/r09_port_deviation_*.txt.)
 //
 // fused (LDSCAM only): no cam_update launch in front.  Every workgroup fills its LDS table of dy from active / scale_c / rhs
 // -- the sweep reads NO w.dy from global memory, which another workgroup of this launch may not have written yet -- and the
 // LAST workgroup (one per 256 cameras) runs cam_update_body, a thread per camera (w.dy, the candidate cameras, cam_part: read
 // by later launches only).  The last ones because their wavefronts have the fewest points when P is no multiple of the
 // launch's stride.
-template <int KD, bool LDSCAM, int LPP, bool LONGT = false, bool DIR = true>
+template <int KD, bool LDSCAM, int LPP, bool LONGT = false>
 __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem pb, Ws w, int fused) {
-  constexpr int BD = 6 + KD;
   __shared__ double red[4][3];
-  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy[6C + KD NI = n_red], and DIR = false: flags[C] (bytes)
+  extern __shared__ double cam_cache[];   // LDSCAM: R[9C] t[3C] dy[6C + KD NI = n_red]
   if (w.ctl->done) return;
   const Dims& d = pb.d;
   constexpr int PPW = 64 / LPP;
@@ -2401,15 +2395,9 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
   const double* lt = lq + 9 * d.C;
   const double* ldy = lt + 3 * d.C;
   const double* ldi = ldy + 6 * d.C;              // the intrinsics entries of dy [KD NI]
-  // DIR = false: the cameras' constant-parameter flags [C] (DIR needs no masks).  Bytes: with doubles the table of 400 cameras
-  // with their own intrinsics would not fit into 64 KB
-  const uint8_t* lfl = reinterpret_cast<const uint8_t*>(ldi + KD * d.NI);
   if (LDSCAM) {
     double* cc = cam_cache;
-    for (int i = threadIdx.x; i < d.C; i += 256) {
-      quat_to_R(pb.cam_q + 4 * i, cc + 9 * i);
-      if (!DIR) reinterpret_cast<uint8_t*>(cc + 12 * d.C + d.n_red)[i] = pb.cam_const ? pb.cam_const[i] : (uint8_t)0;
-    }
+    for (int i = threadIdx.x; i < d.C; i += 256) quat_to_R(pb.cam_q + 4 * i, cc + 9 * i);
     for (int i = threadIdx.x; i < 3 * d.C; i += 256) cc[9 * d.C + i] = pb.cam_t[i];
     // dy: the poses' entries first, then the intrinsics', as in w.dy
     if (fused) {
@@ -2421,7 +2409,7 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
       const int nbody = min((int)gridDim.x, (d.C + 256) / 256);
       const int jb = (int)gridDim.x - 1 - (int)blockIdx.x;
       if (jb < nbody) {
-        for (int c = jb * 256 + threadIdx.x; c <= d.C; c += 256 * nbody) cam_update_body<KD>(pb, w, c, DIR);
+        for (int c = jb * 256 + threadIdx.x; c <= d.C; c += 256 * nbody) cam_update_body<KD>(pb, w, c);
         if (jb == 0 && threadIdx.x == 0) w.ctl->fused_step_prologues += 1;
       }
     } else {
@@ -2430,7 +2418,7 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
     }
     __syncthreads();
   }
-  (void)lfl; (void)ldi;
+  (void)ldi;
   // same software pipeline over the points of a wavefront as in point_pass_kernel
   int p = (blockIdx.x * 4 + wave) * PPW + sub;
   constexpr int NPF = LONGT ? 4 : 2;             // prefetched observations per lane (see point_pass_kernel)
@@ -2490,54 +2478,37 @@ __global__ __launch_bounds__(256, VGG_PS_OCC) void point_step_kernel(DevProblem 
       const int c = f_pf.cam(pass, pb.obs_cam, o);
       const float2 uv = f_pf.uv(pass, pb.obs_uv, o);
       const int a = d.shared ? 0 : c;
-      if constexpr (DIR) {
-        double dyp[6], di[2] = {0.0, 0.0};
+      double dyp[6], di[2] = {0.0, 0.0};
 #pragma unroll
-        for (int k = 0; k < 6; ++k) dyp[k] = LDSCAM ? ldy[6 * c + k] : w.dy[6 * c + k];
+      for (int k = 0; k < 6; ++k) dyp[k] = LDSCAM ? ldy[6 * c + k] : w.dy[6 * c + k];
 #pragma unroll
-        for (int k = 0; k < KD; ++k) di[k] = LDSCAM ? ldi[KD * a + k] : w.dy[6 * d.C + KD * a + k];
-        const double df = (KD == 2 || (KD == 1 && !d.only_k)) ? di[0] : 0.0;
-        const double dk = (KD == 2) ? di[1] : ((KD == 1 && d.only_k) ? di[0] : 0.0);
-        double Rg[9];
-        const double* Rc = lq + 9 * c;
-        if (!LDSCAM) { quat_to_R(pb.cam_q + 4 * c, Rg); Rc = Rg; }
-        const ObsStep s = obs_step_R(d.model, Rc, LDSCAM ? lt + 3 * c : pb.cam_t + 3 * c, pb.intr + 4 * a, X, dyp, df, dk,
-                                     (double)uv.x, (double)uv.y);
-        double y[2] = {s.fy[0], s.fy[1]};
-        if (d.loss != kLossTrivial) {
-          const double sq = s.r[0] * s.r[0] + s.r[1] * s.r[1];
-          double rho[3];
-          loss_eval(d.loss, d.loss_scale, sq, rho);
-          const Corrector cor(sq, rho);
+      for (int k = 0; k < KD; ++k) di[k] = LDSCAM ? ldi[KD * a + k] : w.dy[6 * d.C + KD * a + k];
+      const double df = (KD == 2 || (KD == 1 && !d.only_k)) ? di[0] : 0.0;
+      const double dk = (KD == 2) ? di[1] : ((KD == 1 && d.only_k) ? di[0] : 0.0);
+      double Rg[9];
+      const double* Rc = lq + 9 * c;
+      if (!LDSCAM) { quat_to_R(pb.cam_q + 4 * c, Rg); Rc = Rg; }
+      const ObsStep s = obs_step_R(d.model, Rc, LDSCAM ? lt + 3 * c : pb.cam_t + 3 * c, pb.intr + 4 * a, X, dyp, df, dk,
+                                   (double)uv.x, (double)uv.y);
+      double y[2] = {s.fy[0], s.fy[1]};
+      if (d.loss != kLossTrivial) {
+        const double sq = s.r[0] * s.r[0] + s.r[1] * s.r[1];
+        double rho[3];
+        loss_eval(d.loss, d.loss_scale, sq, rho);
+        const Corrector cor(sq, rho);
 #pragma unroll
-          for (int rep = 0; rep < 2; ++rep) {        // fy' = C fy, then C fy' for the adjoint
-            const double rty = cor.alpha_sq_norm * (s.r[0] * y[0] + s.r[1] * y[1]);
-            y[0] = cor.sqrt_rho1 * (y[0] - s.r[0] * rty);
-            y[1] = cor.sqrt_rho1 * (y[1] - s.r[1] * rty);
-          }
+        for (int rep = 0; rep < 2; ++rep) {        // fy' = C fy, then C fy' for the adjoint
+          const double rty = cor.alpha_sq_norm * (s.r[0] * y[0] + s.r[1] * y[1]);
+          y[0] = cor.sqrt_rho1 * (y[0] - s.r[0] * rty);
+          y[1] = cor.sqrt_rho1 * (y[1] - s.r[1] * rty);
         }
-        double v3[3];
-        s.adjoint(y, v3);
-        if (!pt_c) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) t3[k] += Rc[k] * v3[0] + Rc[3 + k] * v3[1] + Rc[6 + k] * v3[2];
-        }
-        return;
       }
-      double r[2], F[2 * BD], E[6];
-      if (LDSCAM)
-        eval_full<KD>(d, lq + 9 * c, lt + 3 * c, pb.intr + 4 * a, X, uv, (unsigned)lfl[c],
-                      pb.intr_const ? pb.intr_const[a] != 0 : false, pt_c, r, F, E);
-      else
-        eval_full<KD>(d, CamR(pb.cam_q + 4 * c).R, pb.cam_t + 3 * c, pb.intr + 4 * a, X, uv,
-                      pb.cam_const ? pb.cam_const[c] : 0u, pb.intr_const ? pb.intr_const[a] != 0 : false, pt_c, r, F, E);
-      double fy0 = 0, fy1 = 0;
+      double v3[3];
+      s.adjoint(y, v3);
+      if (!pt_c) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) { const double v = LDSCAM ? ldy[6 * c + k] : w.dy[6 * c + k]; fy0 += F[k] * v; fy1 += F[BD + k] * v; }
-#pragma unroll
-      for (int k = 0; k < KD; ++k) { const double v = LDSCAM ? ldi[KD * a + k] : w.dy[6 * d.C + KD * a + k]; fy0 += F[6 + k] * v; fy1 += F[BD + 6 + k] * v; }
-      t3[0] += E[0] * fy0 + E[3] * fy1; t3[1] += E[1] * fy0 + E[4] * fy1; t3[2] += E[2] * fy0 + E[5] * fy1;
-      s_mcc += fy0 * (r[0] - 0.5 * fy0) + fy1 * (r[1] - 0.5 * fy1);
+        for (int k = 0; k < 3; ++k) t3[k] += Rc[k] * v3[0] + Rc[3 + k] * v3[1] + Rc[6 + k] * v3[2];
+      }
     };
     for (int o = o0 + sl; o < o1; o += LPP) evaluated((o - o0) / LPP, o);
 #pragma unroll
@@ -2958,6 +2929,21 @@ static bool every_group_has_diagonal_tile(const Launch& L) {
   return true;
 }
 
+// run-time value -> template argument: the refined intrinsics per block (kd), the lanes per point of the point passes (lpp)
+template <typename Fn0, typename Fn1, typename Fn2>
+static int dispatch_kd(int kd, Fn0 f0, Fn1 f1, Fn2 f2) {
+  switch (kd) { case 0: return f0(); case 1: return f1(); default: return f2(); }
+}
+template <typename Fn>
+static void dispatch_lpp(int lpp, Fn fn) {
+  switch (lpp) {
+    case 8: fn(std::integral_constant<int, 8>{}); break;
+    case 16: fn(std::integral_constant<int, 16>{}); break;
+    case 32: fn(std::integral_constant<int, 32>{}); break;
+    default: fn(std::integral_constant<int, 64>{}); break;
+  }
+}
+
 // which: 0 = the whole phase; 1 = up to the off-diagonal tile launch and the sums of its tiles; 2 = the diagonal launch, its
 // sums and assemble (1 / 2: the split exchange of the sharded solve, phases 7 / 9 -- one tile batch, separate launches)
 template <int KD>
@@ -2998,10 +2984,7 @@ static void phase_schur(const Launch& L, int which = 0) {
         else if (d.shared) launch_cy(lpp, std::true_type{});
         else launch_cy(lpp, std::false_type{});
       };
-      if (L.lpp == 8) launch(std::integral_constant<int, 8>{});
-      else if (L.lpp == 16) launch(std::integral_constant<int, 16>{});
-      else if (L.lpp == 32) launch(std::integral_constant<int, 32>{});
-      else launch(std::integral_constant<int, 64>{});
+      dispatch_lpp(L.lpp, launch);
     }
   }
   if (!L.w.tile_rhs) {
@@ -3070,33 +3053,23 @@ static int phase_step(const Launch& L) {
                                 L.chol_split_a, L.chol_split_b, L.chol_first_blk, true);
   }
   if (rc != VGG_OK) return rc;
-  const bool dir = !g_tuning.legacy_step;
-  // the camera table of point_step in LDS: R, t per camera, dy, and a flag byte per camera for the sweep over full Jacobians
-  const size_t cam_lds = sizeof(double) * (12 * (size_t)d.C + (size_t)d.n_red) + (dir ? 0 : align_up((size_t)d.C, 8));
+  // the camera table of point_step in LDS: R, t per camera, dy
+  const size_t cam_lds = sizeof(double) * (12 * (size_t)d.C + (size_t)d.n_red);
   const bool lds_cam = cam_lds <= 64 * 1024;
   // cam_update's body in point_step's prologue: with the LDS table only (without it the sweep reads w.dy from global memory)
   const int fused = (lds_cam && !g_tuning.legacy_glue) ? 1 : 0;
-  if (!fused) cam_update_kernel<KD><<<div_up(d.C + 1, 64), 64, 0, L.st>>>(L.dp, L.w, dir ? 1 : 0);
+  if (!fused) cam_update_kernel<KD><<<div_up(d.C + 1, 64), 64, 0, L.st>>>(L.dp, L.w);
   {
     ProfScope ps(kProfPointStep, L.st);
-    auto launch = [&](auto lpp, auto dirc) {
+    dispatch_lpp(L.lpp, [&](auto lpp) {
       constexpr int LPP = decltype(lpp)::value;
-      constexpr bool DIR = decltype(dirc)::value;
       const bool longt = long_tracks(LPP, L.d.P, L.d.O);
       if (longt && LPP <= 32) {
-        if (lds_cam) point_step_kernel<KD, true, LPP, (LPP <= 32), DIR><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w, fused);
-        else point_step_kernel<KD, false, LPP, (LPP <= 32), DIR><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w, 0);
-      } else if (lds_cam) point_step_kernel<KD, true, LPP, false, DIR><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w, fused);
-      else point_step_kernel<KD, false, LPP, false, DIR><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w, 0);
-    };
-    auto launch_lpp = [&](auto dirc) {
-      if (L.lpp == 8) launch(std::integral_constant<int, 8>{}, dirc);
-      else if (L.lpp == 16) launch(std::integral_constant<int, 16>{}, dirc);
-      else if (L.lpp == 32) launch(std::integral_constant<int, 32>{}, dirc);
-      else launch(std::integral_constant<int, 64>{}, dirc);
-    };
-    if (dir) launch_lpp(std::true_type{});
-    else launch_lpp(std::false_type{});
+        if (lds_cam) point_step_kernel<KD, true, LPP, (LPP <= 32)><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w, fused);
+        else point_step_kernel<KD, false, LPP, (LPP <= 32)><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w, 0);
+      } else if (lds_cam) point_step_kernel<KD, true, LPP><<<L.wgB, 256, cam_lds, L.st>>>(L.dp, L.w, fused);
+      else point_step_kernel<KD, false, LPP><<<L.wgB, 256, 0, L.st>>>(L.dp, L.w, 0);
+    });
   }
   {
     // the candidate's cost and, should the step be accepted, the next linearisation (bench.py's cam_pass<linearize> slot)
@@ -3178,11 +3151,6 @@ static int make_launch(const vgg_ba_problem* pb, const vgg_ba_options* opt, void
   return VGG_OK;
 }
 
-template <typename Fn0, typename Fn1, typename Fn2>
-static int dispatch_kd(int kd, Fn0 f0, Fn1 f1, Fn2 f2) {
-  switch (kd) { case 0: return f0(); case 1: return f1(); default: return f2(); }
-}
-
 static int run_phase(const Launch& L, int phase) {
   switch (phase) {
     case 0: return VGG_OK;          // (reduce buffer 0 was filled by vgg_ba_begin or, after an accepted step, by phase 3)
@@ -3246,18 +3214,15 @@ int vgg_ba_tuning(int lanes_per_point, int long_tracks, int cam_workgroups, int 
   if (!(lanes_per_point == 0 || lanes_per_point == 8 || lanes_per_point == 16 || lanes_per_point == 32 || lanes_per_point == 64))
     return VGG_ERR_INVALID_ARGUMENT;
   vgg::g_tuning = vgg::Tuning{lanes_per_point, long_tracks < 0 ? -1 : (long_tracks ? 1 : 0), cam_workgroups > 0 ? cam_workgroups : 0,
-                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs, vgg::g_tuning.legacy_glue,
-                              vgg::g_tuning.legacy_step};
+                              point_workgroups > 0 ? point_workgroups : 0, vgg::g_tuning.tile_rhs, vgg::g_tuning.legacy_glue};
   return VGG_OK;
 }
 
 int vgg_ba_set_tile_rhs(int enable) {
-  // bits 0..1: 0 / 1 / 2 as include/vggsfm_amd.h describes them; bit 2: keep the separate glue launches; bit 3: keep the
-  // back-substitution sweep over full Jacobians
-  const bool known = enable >= 0 && enable <= 15 && (enable & 3) <= 2;
+  // bits 0..1: 0 / 1 / 2 as include/vggsfm_amd.h describes them; bit 2: keep the separate glue launches
+  const bool known = enable >= 0 && enable <= 7 && (enable & 3) <= 2;
   vgg::g_tuning.tile_rhs = known ? (enable & 3) : 1;
   vgg::g_tuning.legacy_glue = (known && (enable & 4)) ? 1 : 0;
-  vgg::g_tuning.legacy_step = (known && (enable & 8)) ? 1 : 0;
   return VGG_OK;
 }
 
