@@ -1,5 +1,6 @@
 """VGPRs / scratch / occupancy / LDS of every kernel of a .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python scripts/prof/kernel_resources.py vggsfm_amd/csrc/ba.hip [name filter] [extra hipcc flags...]"""
+usage: python scripts/prof/kernel_resources.py vggsfm_amd/csrc/ba_tiles.hip [name filter] [extra hipcc flags...]
+(the BA kernels: ba_cam.hip, ba_point.hip, ba_tiles.hip, ba_exchange.hip and, for the solve's own small ones, ba.hip)"""
 import re
 import subprocess
 import sys

@@ -33,8 +33,8 @@ cd $ROOT/vggsfm_amd/csrc
 cp ../libvggsfm_amd.so /tmp/lib_product.so
 : > $OUT/ablations.jsonl
 run() {   # label, extra -D flags
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics $2 -c ba.hip -o /tmp/ba_ablate.o 2>/dev/null || { echo "build failed: $1"; return; }
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libvggsfm_amd.so /tmp/ba_ablate.o $(ls _obj/*.o | grep -v "/ba.o")
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics $2 -c ba_tiles.hip -o /tmp/ba_ablate.o 2>/dev/null || { echo "build failed: $1"; return; }
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libvggsfm_amd.so /tmp/ba_ablate.o $(ls _obj/*.o | grep -v "/ba_tiles.o")
   (cd $ROOT && $BENCH 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])

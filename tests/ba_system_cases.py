@@ -158,7 +158,7 @@ def check_edges(name, prob, merged=True):
     odd4 = [t for t, k in tiles.items() if k % 4]
     odd32 = [t for t, k in tiles.items() if k % 32]
     assert odd4 and odd32 and (len(tiles) == 1 or len(set(odd4) | set(odd32)) >= 2), tiles
-    auto_lanes = 16 if O / P <= 72.0 else 32             # (lanes_per_point / long_tracks in csrc/ba.hip)
+    auto_lanes = 16 if O / P <= 72.0 else 32             # (lanes_per_point / long_tracks in csrc/ba_types.hpp)
     auto_long = O > 1.5 * auto_lanes * P
     if name != "k":
         assert auto_lanes == 16 and not auto_long

@@ -124,6 +124,17 @@ def test_library_loads_and_exports_every_declared_symbol():
         assert fn.restype is restype and list(fn.argtypes) == argtypes, name
 
 
+def test_one_copy_of_the_shared_host_state_of_the_ba_units():
+    """The BA launches are spread over several translation units that share the tuning overrides, the profiler and the table
+    of solves: among ALL symbols of the library, of any binding, each is defined exactly once.  (A `static` object in a shared
+    header would give every unit a copy: vgg_ba_tuning would stop reaching the point and camera launchers while every
+    numerical test still passed.)"""
+    nm = subprocess.run(["nm", "--defined-only", "-C", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    names = [line.split(None, 2)[2] for line in nm.splitlines() if len(line.split(None, 2)) == 3]
+    for name in ("vgg::g_tuning", "vgg::g_prof", "vgg::g_host_solves"):
+        assert names.count(name) == 1, (name, names.count(name))
+
+
 def test_the_header_parser_reads_kinds_and_field_order():
     """The comparison above is not vacuous: what the parser reads for a few declarations, pinned by hand (long / int /
     size_t told apart, parameter counts, field order), and a binding with cam_q / cam_t swapped -- same sizeof -- differs."""

@@ -28,9 +28,9 @@ from . import _lib
 from .ba_options import LOSS_ID, TERMINATION, BundleAdjustmentOptions
 
 MODEL_ID = {"SIMPLE_PINHOLE": 0, "SIMPLE_RADIAL": 1}
-GROUP = 16          # cameras per Schur tile side (must match kGroup in csrc/ba.hip)
+GROUP = 16          # cameras per Schur tile side (must match kGroup in csrc/ba_types.hpp)
 CHUNK = 1024        # tile entries per workgroup
-SUB = 32            # entries per strided sub-chunk (kSub in csrc/ba.hip)
+SUB = 32            # entries per strided sub-chunk (kSub in csrc/ba_types.hpp)
 MIN_CHUNK = 128     # lower bound of the adaptive chunk size
 # Single-GPU solves can factorise on a CU-masked stream while the later Schur tile batches run on the other CUs.
 # Correct and bit-reproducible, but measured SLOWER on MI355X in round 1 (3.50 vs 3.09 ms per iteration at 200 x 100k:
@@ -199,7 +199,7 @@ TILE_ORDERS_EXPERIMENTAL = ("stride", "sdm", "msd", "dsm")     # round-5 A/B var
 
 
 def _block_slot_bits(block_rows, group=GROUP):
-    """Per 16-row block b of a tile side, the camera slots with rows in it as a bit mask (block_slot_bits<BD> in csrc/ba.hip):
+    """Per 16-row block b of a tile side, the camera slots with rows in it as a bit mask (block_slot_bits<BD> in csrc/ba_tiles.hip):
     slots 16 b // block_rows .. (16 b + 15) // block_rows.  The tile kernels run block b when one of those cameras is present."""
     return [((2 << min(group - 1, (16 * b + 15) // block_rows)) - 1) & ~((1 << ((16 * b) // block_rows)) - 1)
             for b in range(block_rows * group // 16)]
@@ -472,7 +472,7 @@ def build_schur_tiles(row_ptr, obs_cam, group=GROUP, chunk=CHUNK, max_chunks=Non
     A *segment* is the run of one point's observations that falls into one group of `group`
     consecutive cameras; an *entry* pairs two segments (gI <= gJ) of the same point; entries are
     sorted by tile (gI, gJ) and, inside a tile, by the sweep position of the point (first camera, last camera); a tile with k entries gets J = ceil(k / `chunk`)
-    workgroups ("chunks", off-diagonal tiles first), workgroup j taking the sub-chunks j, j+J, ... of SUB entries (kSub in ba.hip).
+    workgroups ("chunks", off-diagonal tiles first), workgroup j taking the sub-chunks j, j+J, ... of SUB entries (kSub in ba_types.hpp).
     Returns (chunk_desc (n,6) int32 = gI,gJ,tile_begin,tile_end,j,J ; entries (E,4) int32 = point index,
     segA, segB, maskA|maskB<<16 of the QUAD (the union over the four consecutive entries, aligned to the tile's begin, that one
     MFMA K-step packs; bit l of a mask <=> camera group*16 + l observes one of the four points) ;
@@ -834,7 +834,7 @@ def compile_problem(points3d, extrinsics, intrinsics, tracks, masks, extra_param
     # resident schur_tile workgroups per CU (occupancy of the kernel variant): off-diagonal launch 3 (BD = 6) or 2,
     # diagonal launch 4 or 2 -- one full round each
     kd = int(bool(refine_focal_length)) + int(bool(refine_extra_params) and camera_type == "SIMPLE_RADIAL")
-    block_rows = 6 if (shared_camera or kd == 0) else 6 + kd          # BD of schur_tile_kernel (make_dims in csrc/ba.hip)
+    block_rows = 6 if (shared_camera or kd == 0) else 6 + kd          # BD of schur_tile_kernel (csrc/ba_tiles.hip; make_dims in csrc/ba_types.hpp)
     slots = (cus * TILE_WGS_PER_CU[0], cus * TILE_WGS_PER_CU[1]) if block_rows == 6 else (cus * 2, cus * 2)
     if _hook("VGGSFM_TILE_WGS"):                       # measurement hook: workgroups per CU as floats, "off,diag"
         fo, fd = (float(x) for x in _hook("VGGSFM_TILE_WGS").split(","))

@@ -948,7 +948,7 @@ __global__ __launch_bounds__(256, df_occupancy(CHAIN)) void chol_dataflow_kernel
   (void)dtile;
   DF_STAMP(0);
 
-  // Overlap with the Schur tile batches (ba.hip, options.overlap_factorization): the contributions to the columns >=
+  // Overlap with the Schur tile batches (ba_tiles.hip launched by ba.hip, options.overlap_factorization): the contributions to the columns >=
   // ov.first_col are still being summed into S2 by another stream when this launch starts; flag k says that everything
   // for the columns >= ov.wait_col[k] has landed.  A tile waits for the last flag its columns need and adds S2.
   const double* S2 = nullptr;

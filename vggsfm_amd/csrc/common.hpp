@@ -76,7 +76,7 @@ __device__ __forceinline__ double load_f64(const T* p) { return (double)(*p); }
 
 inline int div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
-// Overlap of the factorisation with the computation of the reduced system (ba.hip <-> chol.hip): contributions to
+// Overlap of the factorisation with the computation of the reduced system (ba.hip, ba_tiles.hip <-> chol.hip): contributions to
 // columns >= first_col arrive in a second matrix S2 (same n x n layout) from work running on another stream; device flag k
 // (set by a kernel behind each tile batch) says that every contribution to columns >= wait_col[k] (ascending) is in place.
 // The dataflow factorisation is one launch, so it waits on the device: a tile waits for the last flag its columns need and

@@ -12,7 +12,7 @@
     window_bundle_adjustment                         video_runner.py:800-838  (vggsfm_amd.ba)
     joint_bundle_adjustment                          video_runner.py:494-541
 
-All kernels underneath are the ones of the batch path (pose.hip, geometry.hip, triangulate.hip, ba.hip).
+All kernels underneath are the ones of the batch path (pose.hip, geometry.hip, triangulate.hip, the ba*.hip units).
 """
 import math
 import os
