@@ -261,6 +261,41 @@ class GeometryRunner:
         predictions["unproj_dense_points3D"] = unproj
         return predictions
 
+    # ------------------------------------------------------------------ dense depth from frames (no learned part)
+    def dense_reconstruct_from_frames(self, predictions, images, original_images=None, **options):
+        """The dense stage for users without a depth network: every registered image of predictions["reconstruction"] is
+        swept against its neighbours by plane-sweep stereo and checked against their maps (vggsfm_amd.mvs, `options` are
+        dense_depth_from_frames').  images: the frames the reconstruction was made from, (S,3,H,W) or (1,S,3,H,W) float32
+        in [0, 1], frame i belonging to image id i.  Sets predictions["depth_dict"] and ["depth_conf_dict"] ((H,W) float32
+        device tensors by image name, depth 0 = none) and, with cfg.visual_dense_point_cloud,
+        ["unproj_dense_points3D"] in align_dense_depth_maps' format: per name np.array([xyz, rgb]), the colours from
+        original_images[name] ((H,W,3), 0 .. 255) or, without them, from the frames."""
+        from . import mvs
+
+        rec = predictions["reconstruction"]
+        depth_dict, conf_dict = mvs.dense_depth_from_frames(rec, images, **options)
+        predictions["depth_dict"] = depth_dict
+        predictions["depth_conf_dict"] = conf_dict
+        unproj = None
+        if bool(getattr(self.cfg, "visual_dense_point_cloud", False)):
+            unproj = {}
+            xyz = mvs.unproject_depth_maps(rec, depth_dict)
+            frames = images[0] if images.dim() == 5 else images
+            by_name = {rec.images[i].name: i for i in rec.images}
+            for name, depth in depth_dict.items():
+                valid = (depth != 0).reshape(-1).cpu().numpy()
+                if original_images is not None:
+                    img = original_images[name]
+                    img = img.cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
+                    rgb = (img / 255.0).reshape(-1, 3)[valid]
+                else:
+                    f = frames[by_name[name]]
+                    f = f.expand(3, *f.shape[-2:]) if f.dim() == 2 or f.shape[0] == 1 else f
+                    rgb = f.permute(1, 2, 0).reshape(-1, 3).double().cpu().numpy()[valid]
+                unproj[name] = np.array([xyz[name].cpu().numpy(), rgb])
+        predictions["unproj_dense_points3D"] = unproj
+        return predictions
+
     # ------------------------------------------------------------------ track video (runner.py:445-450)
     def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
         """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
