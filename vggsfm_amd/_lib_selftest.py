@@ -1,0 +1,45 @@
+"""ctypes binding of vggsfm_amd/csrc/selftest/vggsfm_amd_selftest.h (libvggsfm_amd_selftest.so, built for gfx950): entries
+that run the shared __device__ helpers of csrc/ on a caller's data, for the tests.
+
+A library and a table of their own, like the tracker's (``_lib_klt``): the parameter types, ``check`` and ``stream_ptr`` are
+``_lib``'s, and there is NO fallback: a missing library or one built for another target raises."""
+import ctypes
+import os
+
+from ._lib import _I, _INT, _P, bind, check, require_gpu, stream_ptr  # noqa: F401  (re-exported to the tests)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libvggsfm_amd_selftest.so")
+HEADER = "vggsfm_amd_selftest.h"
+HEADER_PATH = os.path.join(_HERE, "csrc", "selftest", HEADER)
+
+# VGGS_* rows of vggs_crosslane's output
+GROUP_SUM_8, GROUP_SUM_16, GROUP_SUM_32, GROUP_SUM_64, WAVE_SUM, WAVE_MAX, WAVE_BCAST, NUM_PRIMS = range(8)
+SCATTER_VALUES = (6, 14, 24, 28, 36, 45)
+
+SIGNATURES = {
+    "vggs_build_arch": (ctypes.c_char_p, []),
+    "vggs_crosslane": (_INT, [_P, _P, _I, _I, _P, _I, _P, _P, _P]),
+}
+EXPORTED = list(SIGNATURES)
+
+_lib = None
+
+
+def lib():
+    """Load the self-test HIP library or fail loudly."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(
+            f"{LIB_PATH} is missing: the gfx950 HIP library of the device self-tests has not been built. Run "
+            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/selftest`). "
+            "vggsfm_amd has no CPU or eager fallback.")
+    L = ctypes.CDLL(LIB_PATH)
+    bind(L, SIGNATURES)
+    arch = L.vggs_build_arch().decode()
+    if arch != "gfx950":
+        raise RuntimeError(f"libvggsfm_amd_selftest.so was built for {arch}, expected gfx950")
+    _lib = L
+    return L

@@ -113,31 +113,8 @@ __device__ __forceinline__ void block_sum(double* v, double* lds /* [4][NV] */, 
   __syncthreads();
 }
 
-// The wave sums of block_sum as a reduce-scatter butterfly: the same xor steps in the same order as wave_sum, but at each step
-// a lane keeps one half of its values -- the low half where the step's lane bit is clear, the high half where it is set --
-// and sends the other half, so a step adds ceil(N / 2) values instead of N: 23 + 12 + 6 + 3 + 2 + 1 additions for 45 values
-// instead of 45 x 6.  The pairing tree of every value is wave_sum's (the keeper adds its partner's partial sum to its own,
-// and a + b = b + a), so the sums are wave_sum's to the last bit; value i ends in ONE lane instead of in all.
-// N: values this lane holds (capacity; the last may be padding where an odd count was halved), n: how many of them are real,
-// base: index of v[0] among the NV values.
-template <int N, int OFF>
-__device__ __forceinline__ void wave_reduce_scatter(double* v, int lane, int n, int base, double* dst) {
-  if constexpr (OFF == 0) {
-    static_assert(N == 1, "64 lanes hold at most 64 values");
-    if (n > 0) dst[base] = v[0];
-  } else {
-    constexpr int H = (N + 1) / 2;
-    const bool hi = (lane & OFF) != 0;
-    double k[H];
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-      const double up = (H + i < N) ? v[H + i] : 0.0;
-      const double send = hi ? v[i] : up, keep = hi ? up : v[i];
-      k[i] = keep + __shfl_xor(send, OFF, 64);
-    }
-    wave_reduce_scatter<H, OFF / 2>(k, lane, hi ? max(n - H, 0) : min(n, H), base + (hi ? H : 0), dst);
-  }
-}
+// block_sum with the wave sums as a reduce-scatter butterfly (crosslane.hpp, wave_reduce_scatter): the same bits, value i of a
+// wavefront ends in ONE lane instead of in all
 template <int NV>
 __device__ __forceinline__ void block_sum_scatter(double* v, double* lds /* [4][NV] */, double* out /* lds [NV] */) {
   static_assert(NV <= 64, "one value per lane at the end");

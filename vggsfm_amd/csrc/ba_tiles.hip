@@ -38,14 +38,6 @@ namespace vgg {
 // NH x NH accumulators in registers for the whole chunk; all MFMAs are unconditional (scalar loop bounds).
 typedef double f64x4_t __attribute__((ext_vector_type(4)));
 
-// value of the lane with the lowest bit of its index flipped (DPP quad_perm [1,0,3,2]: no LDS, no index register)
-__device__ __forceinline__ double dpp_swap_xor1(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
 #ifndef VGG_TILE_TRACE
 #define VGG_TILE_TRACE 0             // debug builds: per-wavefront phase cycle sums of the off-diagonal schur_tile launch
 #endif
@@ -210,7 +202,7 @@ __device__ __forceinline__ void schur_tile_body(const Ws& w, const int32_t* __re
         *reinterpret_cast<double2*>(dst + k * R + cy_row16) = make_double2(m[3 + k], m[k]);
         dst[k * R + cy_row8] = m[k];
 #else
-        const double ok = dpp_swap_xor1(m[k]), o3k = dpp_swap_xor1(m[3 + k]);   // the other half, one component at a time
+        const double ok = row_xor<1>(m[k]), o3k = row_xor<1>(m[3 + k]);   // the other half, one component at a time
         const double t0 = m[4] * m[k] - m[5] * o3k, t1 = m[5] * ok - m[3] * m[k], t2 = m[3] * o3k - m[4] * ok;
         *reinterpret_cast<double2*>(dst + k * R + cy_row16) = cy_top ? make_double2(t0, t1) : make_double2(m[3 + k], ok);
         dst[k * R + cy_row8] = cy_top ? t2 : m[k];
@@ -904,7 +896,7 @@ __device__ __forceinline__ void prep_body(const DevProblem& pb, const Ws& w, con
     if (!d.shared) for (int k = 0; k < KD; ++k) if (w.active[6 * d.C + KD * c + k]) gmax = fmax(gmax, fabs(g[6 + k]));
   }
   // one block reduction for everything (round 4: six 256-thread trees of eight barriers each took 15 us of every iteration):
-  // wave shuffles, then the four wavefronts' partials in a fixed order
+  // wave sums (crosslane.hpp), then the four wavefronts' partials in a fixed order
   sums[0] = cost;
   const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
 #pragma unroll

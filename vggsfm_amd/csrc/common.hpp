@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include "crosslane.hpp"
 
 #define VGG_OK 0
 #define VGG_ERR_INVALID_ARGUMENT (-1)
@@ -27,30 +28,12 @@ constexpr int kWave = 64;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-// full-wave (64 lanes) butterfly reductions; every lane ends with the total
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// sum over the aligned group of W lanes (W = 16, 32, 64) this lane belongs to; every lane of the group gets the total
-template <int W>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
+// (wave_sum, group_sum<W>, wave_max, wave_bcast on doubles: crosslane.hpp)
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
-__device__ __forceinline__ double wave_bcast(double v, int src) { return __shfl(v, src, 64); }
 
 // fixed-order reduction of Q quantities over the 256 threads: halving tree (t, t + 128), (t, t + 64), ...
 template <int Q>
