@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include "../common.hpp"
+#include "mvs_geometry.hpp"
 #include "vggsfm_amd_mvs.h"
 
 namespace vgg {
@@ -16,38 +17,6 @@ struct MvsViews {
   int32_t src_ray[kMaxSources];
   int32_t ref, ref_ray, count;
 };
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// [R|t] (3 x 4, row-major) of view b from view a
-__device__ __forceinline__ void relative_pose(const double* __restrict__ pa, const double* __restrict__ pb, double* out) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) out[4 * i + j] = pb[4 * i] * pa[4 * j] + pb[4 * i + 1] * pa[4 * j + 1] + pb[4 * i + 2] * pa[4 * j + 2];
-    out[4 * i + 3] = pb[4 * i + 3] - (out[4 * i] * pa[3] + out[4 * i + 1] * pa[7] + out[4 * i + 2] * pa[11]);
-  }
-}
-
-// transfer P by T = [R|t] and project with cam = f, cx, cy, k; false: behind the camera (x, y are then not to be used)
-__device__ __forceinline__ bool transfer_project(const double* T, const double* cam, double p0, double p1, double p2, double& x,
-                                                 double& y, double& z) {
-  const double X0 = T[0] * p0 + T[1] * p1 + T[2] * p2 + T[3];
-  const double X1 = T[4] * p0 + T[5] * p1 + T[6] * p2 + T[7];
-  const double X2 = T[8] * p0 + T[9] * p1 + T[10] * p2 + T[11];
-  const double iz = 1.0 / X2;
-  const double a = X0 * iz, b = X1 * iz;
-  const double d = 1.0 + cam[3] * (a * a + b * b);
-  x = cam[0] * (a * d) + cam[1];
-  y = cam[0] * (b * d) + cam[2];
-  z = X2;
-  return X2 > 0.0;
-}
-
-// false for NaN and infinities too
-__device__ __forceinline__ bool inside_image(double x, double y, int H, int W) {
-  return x >= 0.0 && x <= (double)(W - 1) && y >= 0.0 && y <= (double)(H - 1);
-}
 
 // bilinear sample at (x, y); the coordinates are clamped to the image, so the loads stay in bounds whatever (x, y) is
 // (a sample outside is computed and not used)

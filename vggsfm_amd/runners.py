@@ -296,6 +296,22 @@ class GeometryRunner:
         predictions["unproj_dense_points3D"] = unproj
         return predictions
 
+    # ------------------------------------------------------------------ one fused cloud from the depth maps
+    def fuse_dense_point_cloud(self, predictions, images, output_path=None, **options):
+        """The last stage of the dense path: predictions["depth_dict"] (of dense_reconstruct_from_frames or
+        align_dense_depth_maps, (H,W) float32 device tensors by image name) fused into ONE cloud in the gauge of
+        predictions["reconstruction"] (vggsfm_amd.fusion, `options` are fuse_reconstruction's).  images: the frames, frame
+        i belonging to image id i, for the colours; None: no colours.  Sets predictions["fused_point_cloud"], a
+        fusion.FusedCloud of device tensors (xyz, normal, rgb, num_views, view = image id, pixel) with each surface point
+        once; with `output_path` the cloud is also written there as a binary PLY.  No other key changes."""
+        from . import fusion
+
+        cloud = fusion.fuse_reconstruction(predictions["reconstruction"], predictions["depth_dict"], images, **options)
+        predictions["fused_point_cloud"] = cloud
+        if output_path is not None:
+            fusion.write_ply(output_path, cloud)
+        return predictions
+
     # ------------------------------------------------------------------ track video (runner.py:445-450)
     def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
         """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
