@@ -1,0 +1,49 @@
+"""ctypes binding of vggsfm_amd/csrc/patchmatch/vggsfm_amd_patchmatch.h (libvggsfm_amd_pm.so, built for gfx950): the
+entries of the PatchMatch slanted-plane refinement of the multi-view stereo.
+
+A library and a table of their own, like the tracker's, the stereo's and the fusion's: the entries of the other libraries
+and the headers under include/ are closed, counted sets (tests/test_c_abi.py, tests/test_klt_host.py, tests/test_mvs_host.py,
+tests/test_fusion_host.py).  The parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there,
+there is NO fallback: a missing library or one built for another target raises.  tests/test_patchmatch_host.py compares the
+table with the header type by type and with the library's symbols."""
+import ctypes
+import os
+
+from ._lib import _D, _I, _INT, _P, _U, bind, check, require_gpu, stream_ptr  # noqa: F401  (re-exported to patchmatch.py)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libvggsfm_amd_pm.so")
+HEADER = "vggsfm_amd_patchmatch.h"
+HEADER_PATH = os.path.join(_HERE, "csrc", "patchmatch", HEADER)
+
+MAX_SOURCES, MAX_RADIUS = 8, 3                 # VGGR_MAX_* of the header
+
+SIGNATURES = {
+    "vggr_build_arch": (ctypes.c_char_p, []),
+    "vggr_plane_init": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _D, _U, _P, _P]),
+    "vggr_plane_cost": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _D, _P, _P, _P]),
+    "vggr_step": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _D, _D, _D, _D, _D, _D, _U, _I, _I, _P, _P, _P]),
+    "vggr_outputs": (_INT, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P]),
+}
+EXPORTED = list(SIGNATURES)
+
+_lib = None
+
+
+def lib():
+    """Load the PatchMatch refinement's HIP library or fail loudly."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(
+            f"{LIB_PATH} is missing: the gfx950 HIP library of the PatchMatch refinement has not been built. Run "
+            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/patchmatch`). "
+            "vggsfm_amd has no CPU or eager fallback.")
+    L = ctypes.CDLL(LIB_PATH)
+    bind(L, SIGNATURES)
+    arch = L.vggr_build_arch().decode()
+    if arch != "gfx950":
+        raise RuntimeError(f"libvggsfm_amd_pm.so was built for {arch}, expected gfx950")
+    _lib = L
+    return L

@@ -1,5 +1,6 @@
-// The pose, transfer and projection arithmetic that vggsfm_amd_mvs.h states under "Shared by both entries": one copy,
-// included by mvs.hip and by ../fuse/fuse.hip (both parity files, built with -ffp-contract=off).
+// The pose, transfer and projection arithmetic that vggsfm_amd_mvs.h states under "Shared by both entries" and the sweep's
+// bilinear sample: one copy, included by mvs.hip, ../fuse/fuse.hip and ../patchmatch/patchmatch.hip (all parity files,
+// built with -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +36,21 @@ __device__ __forceinline__ bool transfer_project(const double* T, const double* 
 // false for NaN and infinities too
 __device__ __forceinline__ bool inside_image(double x, double y, int H, int W) {
   return x >= 0.0 && x <= (double)(W - 1) && y >= 0.0 && y <= (double)(H - 1);
+}
+
+// bilinear sample at (x, y); the coordinates are clamped to the image, so the loads stay in bounds whatever (x, y) is
+// (a sample outside is computed and not used)
+__device__ __forceinline__ double bilinear(const float* __restrict__ img, int H, int W, double x, double y) {
+  x = fmin(fmax(x, 0.0), (double)(W - 1));
+  y = fmin(fmax(y, 0.0), (double)(H - 1));
+  const double xf = floor(x), yf = floor(y);
+  const int x0 = (int)xf, y0 = (int)yf;
+  const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+  const double fx = x - xf, fy = y - yf;
+  const float* r0 = img + (long)y0 * W;
+  const float* r1 = img + (long)y1 * W;
+  const double i00 = (double)r0[x0], i01 = (double)r0[x1], i10 = (double)r1[x0], i11 = (double)r1[x1];
+  return ((1.0 - fx) * (1.0 - fy)) * i00 + (fx * (1.0 - fy)) * i01 + ((1.0 - fx) * fy) * i10 + (fx * fy) * i11;
 }
 
 }  // namespace vgg

@@ -269,11 +269,23 @@ class GeometryRunner:
         in [0, 1], frame i belonging to image id i.  Sets predictions["depth_dict"] and ["depth_conf_dict"] ((H,W) float32
         device tensors by image name, depth 0 = none) and, with cfg.visual_dense_point_cloud,
         ["unproj_dense_points3D"] in align_dense_depth_maps' format: per name np.array([xyz, rgb]), the colours from
-        original_images[name] ((H,W,3), 0 .. 255) or, without them, from the frames."""
+        original_images[name] ((H,W,3), 0 .. 255) or, without them, from the frames.
+
+        Option patchmatch_iterations (default 0: the sweep alone, as before): with more, the swept maps are refined by
+        that many PatchMatch slanted-plane iterations before the check (vggsfm_amd.patchmatch, whose
+        dense_depth_from_frames then takes `options`, `seed` among them), and predictions["depth_normal_dict"] holds the
+        unit world normals ((H,W,3) float32 device tensors by image name, (0, 0, 0) = none)."""
         from . import mvs
 
         rec = predictions["reconstruction"]
-        depth_dict, conf_dict = mvs.dense_depth_from_frames(rec, images, **options)
+        patchmatch_iterations = int(options.pop("patchmatch_iterations", 0))
+        if patchmatch_iterations > 0:
+            from . import patchmatch
+
+            depth_dict, conf_dict, normal_dict = patchmatch.dense_depth_from_frames(rec, images, patchmatch_iterations, **options)
+            predictions["depth_normal_dict"] = normal_dict
+        else:
+            depth_dict, conf_dict = mvs.dense_depth_from_frames(rec, images, **options)
         predictions["depth_dict"] = depth_dict
         predictions["depth_conf_dict"] = conf_dict
         unproj = None
