@@ -1,0 +1,50 @@
+"""ctypes binding of vggsfm_amd/csrc/tsdf/vggsfm_amd_tsdf.h (libvggsfm_amd_tsdf.so, built for gfx950): the entries of the
+meshing -- TSDF integration of the depth maps and marching tetrahedra on the volume.
+
+A library and a table of their own, like the tracker's, the stereo's, the fusion's and the refinement's: the entries of the
+other libraries and the headers under include/ are closed, counted sets (tests/test_c_abi.py, tests/test_klt_host.py,
+tests/test_mvs_host.py, tests/test_fusion_host.py, tests/test_patchmatch_host.py).  The parameter types, ``check``,
+``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there, there is NO fallback: a missing library or one built for another
+target raises.  tests/test_meshing_host.py compares the table with the header type by type and with the library's symbols."""
+import ctypes
+import os
+
+from ._lib import _D, _I, _INT, _L, _P, bind, check, require_gpu, stream_ptr  # noqa: F401  (re-exported to meshing.py)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libvggsfm_amd_tsdf.so")
+HEADER = "vggsfm_amd_tsdf.h"
+HEADER_PATH = os.path.join(_HERE, "csrc", "tsdf", HEADER)
+
+GROUP, MAX_VIEWS = 256, 256                    # VGGV_GROUP, VGGV_MAX_VIEWS of the header
+MAX_NODES = (2 ** 31 - 1) // 7                 # a grid with more nodes is refused
+
+SIGNATURES = {
+    "vggv_build_arch": (ctypes.c_char_p, []),
+    "vggv_case_table": (_INT, [_P]),
+    "vggv_integrate": (_INT, [_P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _I, _I, _I, _D, _P, _P, _P, _P]),
+    "vggv_mesh_count": (_INT, [_P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
+    "vggv_mesh_emit": (_INT, [_P, _P, _P, _D, _D, _D, _D, _I, _I, _I, _D, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P]),
+}
+EXPORTED = list(SIGNATURES)
+
+_lib = None
+
+
+def lib():
+    """Load the meshing's HIP library or fail loudly."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(
+            f"{LIB_PATH} is missing: the gfx950 HIP library of the meshing has not been built. Run "
+            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/tsdf`). "
+            "vggsfm_amd has no CPU or eager fallback.")
+    L = ctypes.CDLL(LIB_PATH)
+    bind(L, SIGNATURES)
+    arch = L.vggv_build_arch().decode()
+    if arch != "gfx950":
+        raise RuntimeError(f"libvggsfm_amd_tsdf.so was built for {arch}, expected gfx950")
+    _lib = L
+    return L

@@ -324,6 +324,24 @@ class GeometryRunner:
             fusion.write_ply(output_path, cloud)
         return predictions
 
+    # ------------------------------------------------------------------ one surface from the depth maps
+    def mesh_dense_surface(self, predictions, images=None, output_path=None, confidence_weights=False, **options):
+        """The surface of the dense path: predictions["depth_dict"] integrated into a TSDF volume and its zero level set
+        extracted as a triangle mesh in the gauge of predictions["reconstruction"] (vggsfm_amd.meshing, `options` are
+        mesh_reconstruction's: resolution, margin, trunc, min_weight, bounds).  images: the frames, frame i belonging to
+        image id i, for the colours; None: no colours.  confidence_weights: weigh every pixel by
+        predictions["depth_conf_dict"] instead of 1.  Sets predictions["dense_mesh"], a meshing.Mesh of device tensors
+        (vertices, normals, rgb, faces); with `output_path` the mesh is also written there as a binary PLY.  No other key
+        changes."""
+        from . import meshing
+
+        conf = predictions["depth_conf_dict"] if confidence_weights else None
+        mesh = meshing.mesh_reconstruction(predictions["reconstruction"], predictions["depth_dict"], images, conf, **options)
+        predictions["dense_mesh"] = mesh
+        if output_path is not None:
+            meshing.write_mesh_ply(output_path, mesh)
+        return predictions
+
     # ------------------------------------------------------------------ track video (runner.py:445-450)
     def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
         """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
