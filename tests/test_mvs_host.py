@@ -53,6 +53,29 @@ def test_the_other_libraries_keep_their_symbols():
         assert set(re.findall(r" T (vgg[a-z]?_\w+)$", nm, flags=re.M)) == set(table)
 
 
+def test_the_dense_stage_states_its_shared_code_once():
+    """Over the sources and headers under csrc/, comments stripped: one definition of each helper the dense libraries share,
+    and the cost nest (named by its zncc expression) in one file."""
+    csrc = os.path.join(ROOT, "vggsfm_amd", "csrc")
+    code = {}
+    for folder, _, names in os.walk(csrc):
+        for name in names:
+            if name.endswith((".hip", ".hpp", ".h")):
+                path = os.path.join(folder, name)
+                code[os.path.relpath(path, csrc)] = re.sub(r"//[^\n]*", "", open(path).read())
+    assert {"mvs/mvs.hip", "patchmatch/patchmatch.hip", "fuse/fuse.hip", "tsdf/tsdf.hip", "klt/klt.hip", "dense.hip"} <= set(code)
+    for helper in ("relative_pose", "transfer_project", "inside_image", "bilinear", "clampi", "make_views", "block_scan_flag",
+                   "block_scan_int"):
+        # a definition: after a type, the name, its parameters, then the body (a call is followed by ; or an operator)
+        definition = re.compile(r"[\w>*&]\s+" + helper + r"\s*\([^;{}]*\)\s*\{")
+        where = [path for path, text in code.items() for _ in definition.findall(text)]
+        assert len(where) == 1, (helper, where)
+        uses = sum(len(re.findall(r"\b" + helper + r"(?:<\w+>)?\s*\(", text)) for text in code.values())
+        assert uses >= 3, helper                                                    # the definition and at least two calls
+    nest = [path for path, text in code.items() if re.search(r"zncc\s*=\s*den\s*>\s*0\.0\s*\?\s*tab\s*/\s*den", text)]
+    assert nest == ["mvs/mvs_cost.hpp"], nest
+
+
 def test_host_refusals_need_no_device():
     """What the entries refuse is decided on the host, before any launch (sources and ray_index are host arrays): every
     out-of-range argument returns VGG_ERR_INVALID_ARGUMENT, an empty frame is a no-op."""

@@ -227,6 +227,28 @@ def bind(L, signatures):
         fn.restype, fn.argtypes = restype, argtypes
 
 
+_side = {}
+
+
+def load_side_library(path, signatures, arch_entry, what, make_dir):
+    """Load the shared object of csrc/<make_dir> (a library and a table of its own, bound by a ``_lib_*`` module) or fail
+    loudly; loaded once per path."""
+    if path in _side:
+        return _side[path]
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"{path} is missing: the gfx950 HIP library of {what} has not been built. Run "
+            f"`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/{make_dir}`). "
+            "vggsfm_amd has no CPU or eager fallback.")
+    L = ctypes.CDLL(path)
+    bind(L, signatures)
+    arch = getattr(L, arch_entry)().decode()
+    if arch != "gfx950":
+        raise RuntimeError(f"{os.path.basename(path)} was built for {arch}, expected gfx950")
+    _side[path] = L
+    return L
+
+
 def check(rc, what):
     if rc != VGG_OK:
         raise RuntimeError(f"{what} failed: {_ERRORS.get(rc, rc)}")

@@ -7,7 +7,7 @@ header type by type and with the library's symbols."""
 import ctypes
 import os
 
-from ._lib import _D, _I, _INT, _L, _P, _SIZE, _Z, bind, check, require_gpu, stream_ptr  # noqa: F401  (re-exported to klt.py)
+from ._lib import _D, _I, _INT, _L, _P, _SIZE, _Z, check, load_side_library, require_gpu, stream_ptr  # noqa: F401  (re-exported to klt.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvggsfm_amd_klt.so")
@@ -27,23 +27,7 @@ SIGNATURES = {
 }
 EXPORTED = list(SIGNATURES)
 
-_lib = None
-
 
 def lib():
     """Load the tracker's HIP library or fail loudly."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: the gfx950 HIP library of the tracker has not been built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/klt`). "
-            "vggsfm_amd has no CPU or eager fallback.")
-    L = ctypes.CDLL(LIB_PATH)
-    bind(L, SIGNATURES)
-    arch = L.vggk_build_arch().decode()
-    if arch != "gfx950":
-        raise RuntimeError(f"libvggsfm_amd_klt.so was built for {arch}, expected gfx950")
-    _lib = L
-    return L
+    return load_side_library(LIB_PATH, SIGNATURES, "vggk_build_arch", "the tracker", "klt")

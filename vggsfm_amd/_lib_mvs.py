@@ -8,7 +8,7 @@ target raises.  tests/test_mvs_host.py compares the table with the header type b
 import ctypes
 import os
 
-from ._lib import _D, _I, _INT, _P, bind, check, require_gpu, stream_ptr  # noqa: F401  (re-exported to mvs.py)
+from ._lib import _D, _I, _INT, _P, check, load_side_library, require_gpu, stream_ptr  # noqa: F401  (re-exported to mvs.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvggsfm_amd_mvs.so")
@@ -24,23 +24,7 @@ SIGNATURES = {
 }
 EXPORTED = list(SIGNATURES)
 
-_lib = None
-
 
 def lib():
     """Load the multi-view stereo HIP library or fail loudly."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: the gfx950 HIP library of the multi-view stereo has not been built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/mvs`). "
-            "vggsfm_amd has no CPU or eager fallback.")
-    L = ctypes.CDLL(LIB_PATH)
-    bind(L, SIGNATURES)
-    arch = L.vggm_build_arch().decode()
-    if arch != "gfx950":
-        raise RuntimeError(f"libvggsfm_amd_mvs.so was built for {arch}, expected gfx950")
-    _lib = L
-    return L
+    return load_side_library(LIB_PATH, SIGNATURES, "vggm_build_arch", "the multi-view stereo", "mvs")

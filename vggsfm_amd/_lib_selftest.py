@@ -6,7 +6,7 @@ A library and a table of their own, like the tracker's (``_lib_klt``): the param
 import ctypes
 import os
 
-from ._lib import _I, _INT, _P, bind, check, require_gpu, stream_ptr  # noqa: F401  (re-exported to the tests)
+from ._lib import _I, _INT, _P, check, load_side_library, require_gpu, stream_ptr  # noqa: F401  (re-exported to the tests)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvggsfm_amd_selftest.so")
@@ -23,23 +23,7 @@ SIGNATURES = {
 }
 EXPORTED = list(SIGNATURES)
 
-_lib = None
-
 
 def lib():
     """Load the self-test HIP library or fail loudly."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: the gfx950 HIP library of the device self-tests has not been built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C vggsfm_amd/csrc/selftest`). "
-            "vggsfm_amd has no CPU or eager fallback.")
-    L = ctypes.CDLL(LIB_PATH)
-    bind(L, SIGNATURES)
-    arch = L.vggs_build_arch().decode()
-    if arch != "gfx950":
-        raise RuntimeError(f"libvggsfm_amd_selftest.so was built for {arch}, expected gfx950")
-    _lib = L
-    return L
+    return load_side_library(LIB_PATH, SIGNATURES, "vggs_build_arch", "the device self-tests", "selftest")

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "scan.hpp"
 #include "../../include/vggsfm_amd.h"
 
 namespace vgg {
@@ -71,23 +72,6 @@ __device__ long block_sum_l(long v, long* red) {
   long t = 0;
   for (int w = 0; w < kAlignWaves; ++w) t += red[w];
   return t;
-}
-
-// exclusive prefix of `flag` over the block in thread order; *total = number of set flags
-__device__ int block_scan_flag(bool flag, int* wave_cnt, int* total) {
-  const unsigned long long b = __ballot(flag);
-  const int lane = lane_id(), w = threadIdx.x / kWave;
-  const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wave_cnt[w] = __popcll(b);
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int k = 0; k < kAlignWaves; ++k) {
-    if (k < w) before += wave_cnt[k];
-    all += wave_cnt[k];
-  }
-  *total = all;
-  return before + in_wave;
 }
 
 // k-th smallest (0-based) of M positive doubles: radix select on the IEEE bit pattern (monotone for x >= 0)
@@ -221,7 +205,7 @@ __global__ __launch_bounds__(kAlignThreads) void depth_align_kernel(
       inlier[o] = 0;
     }
     int total;
-    const int pos = block_scan_flag(keep, sh.wave_cnt, &total);
+    const int pos = block_scan_flag<kAlignWaves>(keep, sh.wave_cnt, &total);
     if (keep) {
       X[M + pos] = x;
       Y[M + pos] = y;

@@ -3,45 +3,22 @@
 #include <math.h>
 
 #include "../common.hpp"
-#include "../mvs/mvs_geometry.hpp"
+#include "../scan.hpp"
+#include "../mvs/mvs_views.hpp"
 #include "vggsfm_amd_fuse.h"
 
 namespace vgg {
 
 constexpr int kTile = 16;                       // normals: 16 x 16 pixels per workgroup, staged with a halo of 1
-constexpr int kMaxSources = VGGF_MAX_SOURCES;
+static_assert(kMaxSources == VGGF_MAX_SOURCES, "mvs_views.hpp and vggsfm_amd_fuse.h disagree");
 constexpr int kNormalViews = 256;               // views per launch of the normals kernel
 constexpr int kFuseThreads = 256, kFuseWaves = kFuseThreads / kWave;
 
-// by-value kernel arguments, validated on the host
+// by-value kernel argument, validated on the host
 struct NormalViews {
   int32_t first;
   int32_t ray[kNormalViews];
 };
-struct FuseViews {
-  int32_t src[kMaxSources];
-  int32_t src_ray[kMaxSources];
-  int32_t view, view_ray, count;
-};
-
-// exclusive prefix of `flag` over the workgroup in thread order; *total = number of set flags (the order of dense.hip's
-// block_scan_flag: ballot and the bits below the lane, then the wavefronts' counts)
-__device__ __forceinline__ int block_scan_flag(bool flag, int* wave_cnt, int* total) {
-  const unsigned long long b = __ballot(flag);
-  const int lane = lane_id(), w = threadIdx.x / kWave;
-  const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wave_cnt[w] = __popcll(b);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kFuseWaves; ++k) {
-    before += k < w ? wave_cnt[k] : 0;
-    all += wave_cnt[k];
-  }
-  *total = all;
-  return before + in_wave;
-}
 
 // ----------------------------------------------------------------------------------------------------------- normals
 // One workgroup per 16 x 16 tile of one view (blockIdx.z), one pixel per lane.  The camera-frame points of the tile and
@@ -105,33 +82,26 @@ __global__ __launch_bounds__(256) void fuse_normals_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------------ fusion
-// One lane per pixel of the view; lanes m < count first derive both relative poses of source m (as mvs_filter_kernel
-// does) and copy its pose and camera.  Every pixel writes stage_views (0: no point), a pixel that emits its staged point
-// and its claims; the workgroup writes its number of points.
+// One lane per pixel of the view (views.ref); the poses are staged and a source's confirmation is tested as in
+// mvs_filter_kernel (mvs_views.hpp), and lanes m <= count copy the poses themselves.  Every pixel writes stage_views
+// (0: no point), a pixel that emits its staged point and its claims; the workgroup writes its number of points.
 __global__ __launch_bounds__(kFuseThreads) void fuse_view_kernel(
     const float* __restrict__ depth, const float* __restrict__ normals, const float* __restrict__ frames,
     const double* __restrict__ poses, const double* __restrict__ cams, const double* __restrict__ rays, int H, int W,
-    FuseViews views, double rel_depth_tol, double reproj_tol, double min_normal_cos, int min_views, uint8_t* claimed,
+    DenseViews views, double rel_depth_tol, double reproj_tol, double min_normal_cos, int min_views, uint8_t* claimed,
     int32_t* __restrict__ stage_views, double* __restrict__ stage_xyz, float* __restrict__ stage_normal,
     float* __restrict__ stage_rgb, int32_t* __restrict__ block_counts) {
-  __shared__ double s_fwd[kMaxSources][12];      // source from view
-  __shared__ double s_bwd[kMaxSources][12];      // view from source
+  __shared__ ViewPoses s_rel;
   __shared__ double s_pose[kMaxSources + 1][12]; // the sources', then the view's
-  __shared__ double s_cam[kMaxSources + 1][4];
   __shared__ int s_pix[kMaxSources][kFuseThreads];   // per lane the pixel of source m that confirms it, or -1
   __shared__ int s_wave[kFuseWaves];
   const int tid = threadIdx.x;
   const int M = views.count;
+  stage_view_poses(s_rel, poses, cams, views);
   if (tid <= M) {
-    const int s = tid < M ? views.src[tid] : views.view, slot = tid < M ? tid : kMaxSources;
-    if (tid < M) {
-      relative_pose(poses + 12 * views.view, poses + 12 * s, s_fwd[tid]);
-      relative_pose(poses + 12 * s, poses + 12 * views.view, s_bwd[tid]);
-    }
+    const int s = tid < M ? views.src[tid] : views.ref, slot = tid < M ? tid : kMaxSources;
 #pragma unroll
     for (int c = 0; c < 12; ++c) s_pose[slot][c] = poses[12 * s + c];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s_cam[slot][c] = cams[4 * s + c];
   }
   __syncthreads();
   const long plane = (long)H * W;
@@ -139,7 +109,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_view_kernel(
   const bool live = p < plane;
   const long pc = live ? p : plane - 1;            // a lane past the frame works on the last pixel and stores nothing
   const int y = (int)(pc / W), x = (int)(pc - (long)y * W);
-  const long vp = views.view * plane + pc;
+  const long vp = views.ref * plane + pc;
   const double z = (double)depth[vp];
   const bool seed = live && z > 0.0 && claimed[vp] == 0;
   const bool with_normals = normals != nullptr, with_rgb = frames != nullptr;
@@ -148,7 +118,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_view_kernel(
   double n_seed[3] = {0.0, 0.0, 0.0};
   bool seed_normal = false;
   if (seed) {
-    const double* ray = rays + 2 * (views.view_ray * plane + pc);
+    const double* ray = rays + 2 * (views.ref_ray * plane + pc);
     const double P0 = ray[0] * z, P1 = ray[1] * z;
     {
       const double* T = s_pose[kMaxSources];
@@ -167,24 +137,14 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_view_kernel(
     }
     if (with_rgb) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) C[c] = (double)frames[(views.view * 3L + c) * plane + pc];
+      for (int c = 0; c < 3; ++c) C[c] = (double)frames[(views.ref * 3L + c) * plane + pc];
     }
     for (int m = 0; m < M; ++m) {
       s_pix[m][tid] = -1;
-      double xs, ys, zc;
-      if (!transfer_project(s_fwd[m], s_cam[m], P0, P1, z, xs, ys, zc)) continue;
-      const double xi = floor(xs + 0.5), yi = floor(ys + 0.5);
-      if (!inside_image(xi, yi, H, W)) continue;
-      const long ps = (long)yi * W + (long)xi;
-      const long sp = views.src[m] * plane + ps;
-      const double zs = (double)depth[sp];
-      if (!(zs > 0.0)) continue;
-      const double* rs = rays + 2 * (views.src_ray[m] * plane + ps);
-      const double Q0 = rs[0] * zs, Q1 = rs[1] * zs;
-      double xb, yb, zb;
-      if (!transfer_project(s_bwd[m], s_cam[kMaxSources], Q0, Q1, zs, xb, yb, zb)) continue;
-      const double ex = xb - (double)x, ey = yb - (double)y;
-      if (!(sqrt(ex * ex + ey * ey) <= reproj_tol && fabs(zb - z) / z <= rel_depth_tol)) continue;
+      SourceHit hit;
+      if (!source_confirms(s_rel, views, m, depth, rays, H, W, x, y, P0, P1, z, reproj_tol, rel_depth_tol, hit)) continue;
+      const long ps = hit.ps, sp = views.src[m] * plane + ps;
+      const double Q0 = hit.q0, Q1 = hit.q1, zs = hit.zs;
       double ns[3] = {0.0, 0.0, 0.0};
       bool src_normal = false;
       if (with_normals) {
@@ -230,7 +190,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_view_kernel(
   }
   if (live) stage_views[p] = emit ? nv : 0;
   int total;
-  block_scan_flag(emit, s_wave, &total);
+  block_scan_flag<kFuseWaves>(emit, s_wave, &total);
   if (tid == 0) block_counts[blockIdx.x] = total;
 }
 
@@ -252,7 +212,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_compact_kernel(
   const long p = (long)blockIdx.x * kFuseThreads + tid;
   const int nv = p < plane ? stage_views[p] : 0;
   int total;
-  const int pos = block_scan_flag(nv > 0, s_wave, &total);   // (its barriers also publish s_before)
+  const int pos = block_scan_flag<kFuseWaves>(nv > 0, s_wave, &total);   // (its barriers also publish s_before)
   long before = 0;
 #pragma unroll
   for (int k = 0; k < kFuseWaves; ++k) before += s_before[k];
@@ -274,13 +234,6 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_compact_kernel(
     out_pixel[row] = (int32_t)p;
   }
   if (blockIdx.x == gridDim.x - 1 && tid == 0) count_out[0] = (int64_t)(first + total);
-}
-
-static bool ray_index_ok(const int32_t* ray_index, int num_frames, int num_rays) {
-  if (!ray_index || num_rays < 1 || num_frames < 1) return false;
-  for (int s = 0; s < num_frames; ++s)
-    if (ray_index[s] < 0 || ray_index[s] >= num_rays) return false;
-  return true;
 }
 
 }  // namespace vgg
@@ -319,19 +272,9 @@ int vggf_fuse_view(const float* depth, const float* normals, const float* frames
                    float* stage_normal, float* stage_rgb, int32_t* block_counts, const int64_t* count_in, int64_t* count_out,
                    long capacity, double* out_xyz, float* out_normal, float* out_rgb, int32_t* out_num_views,
                    int32_t* out_view, int32_t* out_pixel, void* stream) {
-  if (height < 0 || width < 0 || !ray_index_ok(ray_index, num_frames, num_rays) || view < 0 || view >= num_frames ||
-      num_sources < 0 || num_sources > kMaxSources || (num_sources > 0 && !sources))
+  DenseViews views;
+  if (height < 0 || width < 0 || !ray_index || !make_views(num_frames, view, sources, num_sources, 0, ray_index, num_rays, &views))
     return VGG_ERR_INVALID_ARGUMENT;
-  FuseViews views;
-  memset(&views, 0, sizeof(views));
-  views.view = view;
-  views.view_ray = ray_index[view];
-  views.count = num_sources;
-  for (int m = 0; m < num_sources; ++m) {
-    if (sources[m] < 0 || sources[m] >= num_frames || sources[m] == view) return VGG_ERR_INVALID_ARGUMENT;
-    views.src[m] = sources[m];
-    views.src_ray[m] = ray_index[sources[m]];
-  }
   if (min_views < 1 || min_views > num_sources + 1 || !(rel_depth_tol >= 0.0) || !(reproj_tol >= 0.0) ||
       min_normal_cos != min_normal_cos || capacity < 0)
     return VGG_ERR_INVALID_ARGUMENT;

@@ -1,6 +1,7 @@
 // Pyramidal Lucas-Kanade tracker and Shi-Tomasi detector for gfx950: the entries of vggsfm_amd_klt.h.
 // A parity file: built with -ffp-contract=off, every sum in a stated order (tests/klt_cases.py restates it in NumPy).
 #include "../common.hpp"
+#include "../mvs/mvs_geometry.hpp"
 #include "vggsfm_amd_klt.h"
 
 namespace vgg {
@@ -35,8 +36,6 @@ static bool pyramid_layout(int H, int W, int levels, PyramidLayout* L) {
   L->total = off;
   return true;
 }
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------------------------------------------------ pyramid
 __global__ __launch_bounds__(256) void klt_grey_kernel(const float* __restrict__ frames, int channels, long pixels,
@@ -130,23 +129,7 @@ __global__ __launch_bounds__(256) void klt_maxima_kernel(const double* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------ LK step
-// bilinear sample at (x, y), coordinates clamped to the image
-__device__ __forceinline__ double bilinear(const float* __restrict__ img, int H, int W, double x, double y) {
-  x = fmin(fmax(x, 0.0), (double)(W - 1));
-  y = fmin(fmax(y, 0.0), (double)(H - 1));
-  const double xf = floor(x), yf = floor(y);
-  const int x0 = (int)xf, y0 = (int)yf;
-  const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-  const double fx = x - xf, fy = y - yf;
-  const float* r0 = img + (long)y0 * W;
-  const float* r1 = img + (long)y1 * W;
-  const double i00 = (double)r0[x0], i01 = (double)r0[x1], i10 = (double)r1[x0], i11 = (double)r1[x1];
-  double s = ((1.0 - fx) * (1.0 - fy)) * i00 + (fx * (1.0 - fy)) * i01;
-  s = s + ((1.0 - fx) * fy) * i10;
-  s = s + (fx * fy) * i11;
-  return s;
-}
-
+// (clampi and the bilinear sample, coordinates clamped to the image: ../mvs/mvs_geometry.hpp)
 __device__ __forceinline__ double min_eig2(double gxx, double gxy, double gyy) {
   const double diff = gxx - gyy;
   return 0.5 * ((gxx + gyy) - sqrt(diff * diff + 4.0 * (gxy * gxy)));

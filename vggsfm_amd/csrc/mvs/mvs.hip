@@ -3,120 +3,35 @@
 #include <math.h>
 
 #include "../common.hpp"
-#include "mvs_geometry.hpp"
+#include "mvs_cost.hpp"
 #include "vggsfm_amd_mvs.h"
 
 namespace vgg {
 
 constexpr int kTile = 16;                       // 16 x 16 reference pixels per workgroup, one wavefront per 16 x 4 block
-constexpr int kMaxSources = VGGM_MAX_SOURCES;
-
-// by-value kernel argument: the views of one call (validated on the host)
-struct MvsViews {
-  int32_t src[kMaxSources];
-  int32_t src_ray[kMaxSources];
-  int32_t ref, ref_ray, count;
-};
+static_assert(kMaxSources == VGGM_MAX_SOURCES, "mvs_views.hpp and vggsfm_amd_mvs.h disagree");
 
 // ------------------------------------------------------------------------------------------------------------ sweep
-// One workgroup per 16 x 16 tile of reference pixels, one pixel per lane.  The tile with its halo of R pixels and the
-// rays of those pixels are staged in LDS once (clamped to the image, so a lane past the image's edge works on a copy of
-// an edge pixel and only its store is guarded); lanes m < count derive the relative pose of source m.  Then planes,
-// sources, window: no cost volume is kept, a lane carries the previous plane's cost, the best cost and index and the
-// costs before and after the best (the one after is captured on the next plane).  Validity is carried by selects.
+// One workgroup per 16 x 16 tile of reference pixels, one pixel per lane, row-major (mvs_cost.hpp stages the tile and
+// states the cost).  Planes outside, one 1 / w per plane: no cost volume is kept, a lane carries the previous plane's cost,
+// the best cost and index and the costs before and after the best (the one after is captured on the next plane).
 template <int R>
 __global__ __launch_bounds__(256) void mvs_sweep_kernel(const float* __restrict__ frames, const double* __restrict__ poses,
                                                        const double* __restrict__ cams, const double* __restrict__ rays, int H,
-                                                       int W, MvsViews views, double w_far, double dw, int D, int min_views,
+                                                       int W, DenseViews views, double w_far, double dw, int D, int min_views,
                                                        double min_variance, double min_conf, float* __restrict__ out_depth,
                                                        float* __restrict__ out_conf, int32_t* __restrict__ out_index,
                                                        double* __restrict__ out_cost) {
-  constexpr int SIDE = kTile + 2 * R, NPIX = SIDE * SIDE;
-  constexpr double n = (double)((2 * R + 1) * (2 * R + 1));
-  __shared__ float s_img[NPIX];
-  __shared__ double s_ray[NPIX][2];
-  __shared__ double s_rel[kMaxSources][12];
-  __shared__ double s_cam[kMaxSources][4];
-  const int tid = threadIdx.x;
-  const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
-  const long plane = (long)H * W;
-  const int M = views.count;
-  {
-    const float* ref_img = frames + views.ref * plane;
-    for (int i = tid; i < NPIX; i += 256) {
-      const int r = i / SIDE;
-      const long p = (long)clampi(ty0 + r - R, H - 1) * W + clampi(tx0 + (i - r * SIDE) - R, W - 1);
-      s_img[i] = ref_img[p];
-      s_ray[i][0] = rays[2 * p];
-      s_ray[i][1] = rays[2 * p + 1];
-    }
-    if (tid < M) {
-      const int s = views.src[tid];
-      relative_pose(poses + 12 * views.ref, poses + 12 * s, s_rel[tid]);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s_cam[tid][c] = cams[4 * s + c];
-    }
-  }
-  __syncthreads();
-
-  const int lx = tid & 15, ly = tid >> 4;
-  const int centre = (ly + R) * SIDE + (lx + R);
-  // the reference window: mean, then the centred sums
-  double sA = 0.0;
-#pragma unroll
-  for (int dy = -R; dy <= R; ++dy)
-#pragma unroll
-    for (int dx = -R; dx <= R; ++dx) sA += (double)s_img[centre + dy * SIDE + dx];
-  const double mA = sA / n;
-  double sa = 0.0, saa = 0.0;
-#pragma unroll
-  for (int dy = -R; dy <= R; ++dy)
-#pragma unroll
-    for (int dx = -R; dx <= R; ++dx) {
-      const double a = (double)s_img[centre + dy * SIDE + dx] - mA;
-      sa += a;
-      saa += a * a;
-    }
-  const double taa = saa - sa * sa / n;
-  const bool textured = taa / n >= min_variance;
-
+  __shared__ CostTile<R, kTile, kTile> t;
+  cost_stage(t, frames, poses, cams, rays, H, W, views);
+  const CostPixel p = cost_pixel(t, (int)threadIdx.x & 15, (int)threadIdx.x >> 4, H, W, min_variance);
   const double inf = INFINITY;
-  const int x = tx0 + lx, y = ty0 + ly;
-  const bool stored = x < W && y < H;
-  const long pix = (long)min(y, H - 1) * W + min(x, W - 1);
+  const long plane = (long)H * W, pix = p.pix;
+  const bool stored = p.stored;
   double best = inf, c_prev = inf, c_minus = inf, c_plus = inf;
   int best_j = -1;
   for (int j = 0; j < D; ++j) {
-    const double q = 1.0 / (w_far + (double)j * dw);
-    double acc = 0.0;
-    int valid = 0;
-    for (int m = 0; m < M; ++m) {
-      const double* T = s_rel[m];
-      const double* cam = s_cam[m];
-      const float* img = frames + views.src[m] * plane;
-      bool ok = true;
-      double sb = 0.0, sbb = 0.0, sab = 0.0;
-#pragma unroll 1
-      for (int dy = -R; dy <= R; ++dy)
-#pragma unroll
-        for (int dx = -R; dx <= R; ++dx) {
-          const int k = centre + dy * SIDE + dx;
-          double xs, ys, zs;
-          const bool front = transfer_project(T, cam, s_ray[k][0] * q, s_ray[k][1] * q, q, xs, ys, zs);
-          ok = ok && front && inside_image(xs, ys, H, W);
-          const double a = (double)s_img[k] - mA;
-          const double b = bilinear(img, H, W, xs, ys) - mA;
-          sb += b;
-          sbb += b * b;
-          sab += a * b;
-        }
-      const double tbb = sbb - sb * sb / n, tab = sab - sa * sb / n;
-      const double den = sqrt(taa * tbb);
-      const double zncc = den > 0.0 ? tab / den : 0.0;
-      acc = ok ? acc + (1.0 - zncc) : acc;
-      valid += ok ? 1 : 0;
-    }
-    const double cost = (textured && valid >= min_views) ? acc / (double)valid : inf;
+    const double cost = window_cost(t, p, frames, views, H, W, min_views, FrontoParallel{1.0 / (w_far + (double)j * dw)});
     if (out_cost != nullptr) {                       // kernel-uniform
       if (stored) out_cost[(long)j * plane + pix] = cost;
     }
@@ -144,28 +59,17 @@ __global__ __launch_bounds__(256) void mvs_sweep_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ filter
-// One lane per reference pixel; lanes m < count first derive both relative poses of source m.
+// One lane per reference pixel, counting the sources that confirm it (mvs_views.hpp).
 __global__ __launch_bounds__(256) void mvs_filter_kernel(const float* __restrict__ depth, const double* __restrict__ poses,
                                                         const double* __restrict__ cams, const double* __restrict__ rays,
-                                                        int H, int W, MvsViews views, double rel_depth_tol, double reproj_tol,
+                                                        int H, int W, DenseViews views, double rel_depth_tol, double reproj_tol,
                                                         int min_consistent, float* __restrict__ out_depth,
                                                         int32_t* __restrict__ out_count) {
-  __shared__ double s_fwd[kMaxSources][12];      // source from ref
-  __shared__ double s_bwd[kMaxSources][12];      // ref from source
-  __shared__ double s_cam[kMaxSources + 1][4];   // the sources', then ref's
-  const int tid = threadIdx.x;
-  const int M = views.count;
-  if (tid < M) {
-    const int s = views.src[tid];
-    relative_pose(poses + 12 * views.ref, poses + 12 * s, s_fwd[tid]);
-    relative_pose(poses + 12 * s, poses + 12 * views.ref, s_bwd[tid]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s_cam[tid][c] = cams[4 * s + c];
-  }
-  if (tid < 4) s_cam[kMaxSources][tid] = cams[4 * views.ref + tid];
+  __shared__ ViewPoses s;
+  stage_view_poses(s, poses, cams, views);
   __syncthreads();
   const long plane = (long)H * W;
-  const long p = (long)blockIdx.x * 256 + tid;
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= plane) return;
   const int y = (int)(p / W), x = (int)(p - (long)y * W);
   const float zf = depth[views.ref * plane + p];
@@ -174,44 +78,13 @@ __global__ __launch_bounds__(256) void mvs_filter_kernel(const float* __restrict
   if (z > 0.0) {
     const double* ray = rays + 2 * (views.ref_ray * plane + p);
     const double p0 = ray[0] * z, p1 = ray[1] * z;
-    for (int m = 0; m < M; ++m) {
-      double xs, ys, zc;
-      if (!transfer_project(s_fwd[m], s_cam[m], p0, p1, z, xs, ys, zc)) continue;
-      const double xi = floor(xs + 0.5), yi = floor(ys + 0.5);
-      if (!inside_image(xi, yi, H, W)) continue;
-      const long ps = (long)yi * W + (long)xi;
-      const double zs = (double)depth[views.src[m] * plane + ps];
-      if (!(zs > 0.0)) continue;
-      const double* rs = rays + 2 * (views.src_ray[m] * plane + ps);
-      double xb, yb, zb;
-      if (!transfer_project(s_bwd[m], s_cam[kMaxSources], rs[0] * zs, rs[1] * zs, zs, xb, yb, zb)) continue;
-      const double ex = xb - (double)x, ey = yb - (double)y;
-      const bool near = sqrt(ex * ex + ey * ey) <= reproj_tol && fabs(zb - z) / z <= rel_depth_tol;
-      count += near ? 1 : 0;
+    for (int m = 0; m < views.count; ++m) {
+      SourceHit hit;
+      count += source_confirms(s, views, m, depth, rays, H, W, x, y, p0, p1, z, reproj_tol, rel_depth_tol, hit) ? 1 : 0;
     }
   }
   out_count[p] = count;
   out_depth[p] = count >= min_consistent ? zf : 0.0f;
-}
-
-// the views of a call from its host arrays; false: refused
-static bool make_views(int num_frames, int ref, const int32_t* sources, int num_sources, const int32_t* ray_index,
-                       int num_rays, MvsViews* v) {
-  if (num_frames < 1 || ref < 0 || ref >= num_frames || !sources || num_sources < 1 || num_sources > kMaxSources) return false;
-  memset(v, 0, sizeof(*v));
-  v->ref = ref;
-  v->count = num_sources;
-  for (int m = 0; m < num_sources; ++m) {
-    if (sources[m] < 0 || sources[m] >= num_frames || sources[m] == ref) return false;
-    v->src[m] = sources[m];
-  }
-  if (ray_index) {
-    for (int s = 0; s < num_frames; ++s)
-      if (ray_index[s] < 0 || ray_index[s] >= num_rays) return false;
-    v->ref_ray = ray_index[ref];
-    for (int m = 0; m < num_sources; ++m) v->src_ray[m] = ray_index[sources[m]];
-  }
-  return true;
 }
 
 }  // namespace vgg
@@ -226,8 +99,8 @@ int vggm_plane_sweep(const float* frames, const double* poses, const double* cam
                      int height, int width, int ref, const int32_t* sources, int num_sources, double inv_depth_far,
                      double inv_depth_near, int num_planes, int radius, int min_views, double min_variance, double min_conf,
                      float* out_depth, float* out_conf, int32_t* out_index, double* out_cost, void* stream) {
-  MvsViews views;
-  if (height < 0 || width < 0 || !make_views(num_frames, ref, sources, num_sources, nullptr, 0, &views))
+  DenseViews views;
+  if (height < 0 || width < 0 || !make_views(num_frames, ref, sources, num_sources, 1, nullptr, 0, &views))
     return VGG_ERR_INVALID_ARGUMENT;
   if (num_planes < 1 || num_planes > VGGM_MAX_PLANES || radius < 1 || radius > VGGM_MAX_RADIUS || min_views < 1 ||
       min_views > num_sources)
@@ -255,9 +128,9 @@ int vggm_consistency_filter(const float* depth, const double* poses, const doubl
                             const int32_t* ray_index, int num_rays, int num_frames, int height, int width, int ref,
                             const int32_t* sources, int num_sources, double rel_depth_tol, double reproj_tol,
                             int min_consistent, float* out_depth, int32_t* out_count, void* stream) {
-  MvsViews views;
+  DenseViews views;
   if (height < 0 || width < 0 || num_rays < 1 || !ray_index ||
-      !make_views(num_frames, ref, sources, num_sources, ray_index, num_rays, &views))
+      !make_views(num_frames, ref, sources, num_sources, 1, ray_index, num_rays, &views))
     return VGG_ERR_INVALID_ARGUMENT;
   if (min_consistent < 1 || !(rel_depth_tol >= 0.0) || !(reproj_tol >= 0.0)) return VGG_ERR_INVALID_ARGUMENT;
   if (height == 0 || width == 0) return VGG_OK;

@@ -1,6 +1,7 @@
 // The pose, transfer and projection arithmetic that vggsfm_amd_mvs.h states under "Shared by both entries" and the sweep's
-// bilinear sample: one copy, included by mvs.hip, ../fuse/fuse.hip and ../patchmatch/patchmatch.hip (all parity files,
-// built with -ffp-contract=off).
+// bilinear sample: one copy, included (directly or through mvs_views.hpp and mvs_cost.hpp) by mvs.hip, ../fuse/fuse.hip,
+// ../patchmatch/patchmatch.hip, ../tsdf/tsdf.hip, ../klt/klt.hip and ../sim3.hip (all parity files, built with
+// -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 

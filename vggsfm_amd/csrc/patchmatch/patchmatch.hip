@@ -3,20 +3,14 @@
 #include <math.h>
 
 #include "../common.hpp"
-#include "../mvs/mvs_geometry.hpp"
+#include "../mvs/mvs_cost.hpp"
 #include "vggsfm_amd_patchmatch.h"
 
 namespace vgg {
 
 constexpr int kTileX = 32, kTileY = 16;         // 32 x 16 pixels per workgroup: 256 of each colour, one per lane
-constexpr int kMaxSources = VGGR_MAX_SOURCES;
 constexpr int kCandidates = 11;
-
-// by-value kernel argument: the views of one call (validated on the host)
-struct PmViews {
-  int32_t src[kMaxSources];
-  int32_t ref, count;
-};
+static_assert(kMaxSources == VGGR_MAX_SOURCES, "mvs_views.hpp and vggsfm_amd_patchmatch.h disagree");
 
 // what the cost needs besides the plane, by value
 struct PmCost {
@@ -45,125 +39,15 @@ __device__ __forceinline__ bool pm_legal(double al, double be, double ga, double
          wc * wc >= ((cos_tilt * cos_tilt) * ((al * al + be * be) + ga * ga)) * ((u0 * u0 + v0 * v0) + 1.0);
 }
 
+// The tile is staged and the cost stated by mvs_cost.hpp, as for the sweep, with one 1 / w_k per window pixel and source.
 template <int R>
-struct PmTile {
-  static constexpr int SX = kTileX + 2 * R, SY = kTileY + 2 * R, NPIX = SX * SY;
-  float img[NPIX];
-  double ray[NPIX][2];
-  double rel[kMaxSources][12];
-  double cam[kMaxSources][4];
-};
-
-// The tile, its halo of R pixels and their rays, clamped to the frame as the sweep stages them (a lane past the frame's
-// edge works on a copy of an edge pixel and stores nothing); lanes m < count derive the relative pose of source m.
-// Ends with the kernels' only barrier.
-template <int R>
-__device__ __forceinline__ void pm_stage(PmTile<R>& t, const float* __restrict__ frames, const double* __restrict__ poses,
-                                         const double* __restrict__ cams, const double* __restrict__ rays, int H, int W,
-                                         const PmViews& views) {
-  constexpr int SX = PmTile<R>::SX, NPIX = PmTile<R>::NPIX;
-  const int tid = threadIdx.x;
-  const int tx0 = blockIdx.x * kTileX, ty0 = blockIdx.y * kTileY;
-  const float* ref_img = frames + views.ref * ((long)H * W);
-  for (int i = tid; i < NPIX; i += 256) {
-    const int r = i / SX;
-    const long p = (long)clampi(ty0 + r - R, H - 1) * W + clampi(tx0 + (i - r * SX) - R, W - 1);
-    t.img[i] = ref_img[p];
-    t.ray[i][0] = rays[2 * p];
-    t.ray[i][1] = rays[2 * p + 1];
-  }
-  if (tid < views.count) {
-    const int s = views.src[tid];
-    relative_pose(poses + 12 * views.ref, poses + 12 * s, t.rel[tid]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) t.cam[tid][c] = cams[4 * s + c];
-  }
-  __syncthreads();
-}
-
-// a lane's pixel and its reference window, centred once
-struct PmPixel {
-  int x, y, centre;
-  long pix;            // y W + x, clamped into the frame
-  bool stored;
-  double mA, sa, taa;
-  bool textured;
-};
+using PmTile = CostTile<R, kTileX, kTileY>;
 
 // lane -> (2 i + parity(row, colour), row): the 256 pixels of one colour of the 32 x 16 tile
 template <int R>
-__device__ __forceinline__ PmPixel pm_pixel(const PmTile<R>& t, int colour, int H, int W, double min_variance) {
-  constexpr int SX = PmTile<R>::SX;
-  constexpr double n = (double)((2 * R + 1) * (2 * R + 1));
-  const int tid = threadIdx.x;
-  const int ly = tid >> 4, lx = 2 * (tid & 15) + ((ly ^ colour) & 1);      // the tile's origin is even in x and y
-  PmPixel p;
-  p.x = blockIdx.x * kTileX + lx;
-  p.y = blockIdx.y * kTileY + ly;
-  p.centre = (ly + R) * SX + (lx + R);
-  p.stored = p.x < W && p.y < H;
-  p.pix = (long)min(p.y, H - 1) * W + min(p.x, W - 1);
-  double sA = 0.0;
-#pragma unroll
-  for (int dy = -R; dy <= R; ++dy)
-#pragma unroll
-    for (int dx = -R; dx <= R; ++dx) sA += (double)t.img[p.centre + dy * SX + dx];
-  p.mA = sA / n;
-  double sa = 0.0, saa = 0.0;
-#pragma unroll
-  for (int dy = -R; dy <= R; ++dy)
-#pragma unroll
-    for (int dx = -R; dx <= R; ++dx) {
-      const double a = (double)t.img[p.centre + dy * SX + dx] - p.mA;
-      sa += a;
-      saa += a * a;
-    }
-  p.sa = sa;
-  p.taa = saa - sa * sa / n;
-  p.textured = p.taa / n >= min_variance;
-  return p;
-}
-
-// The cost of plane (al, be, ga) at the lane's pixel: the sweep's nest (sources outside, the window inside with its row
-// loop rolled), one 1 / w_k per window pixel and source.  Validity is carried by selects.
-template <int R>
-__device__ __forceinline__ double pm_cost(const PmTile<R>& t, const PmPixel& p, const float* __restrict__ frames,
-                                          const PmViews& views, const PmCost& c, double al, double be, double ga) {
-  constexpr int SX = PmTile<R>::SX;
-  constexpr double n = (double)((2 * R + 1) * (2 * R + 1));
-  const long plane = (long)c.H * c.W;
-  double acc = 0.0;
-  int valid = 0;
-  for (int m = 0; m < views.count; ++m) {
-    const double* T = t.rel[m];
-    const double* cam = t.cam[m];
-    const float* img = frames + views.src[m] * plane;
-    bool ok = true;
-    double sb = 0.0, sbb = 0.0, sab = 0.0;
-#pragma unroll 1
-    for (int dy = -R; dy <= R; ++dy)
-#pragma unroll
-      for (int dx = -R; dx <= R; ++dx) {
-        const int k = p.centre + dy * SX + dx;
-        const double u = t.ray[k][0], v = t.ray[k][1];
-        const double wk = (al * u + be * v) + ga;
-        const double q = 1.0 / wk;
-        double xs, ys, zs;
-        const bool front = transfer_project(T, cam, u * q, v * q, q, xs, ys, zs);
-        ok = ok && wk > 0.0 && front && inside_image(xs, ys, c.H, c.W);
-        const double a = (double)t.img[k] - p.mA;
-        const double b = bilinear(img, c.H, c.W, xs, ys) - p.mA;
-        sb += b;
-        sbb += b * b;
-        sab += a * b;
-      }
-    const double tbb = sbb - sb * sb / n, tab = sab - p.sa * sb / n;
-    const double den = sqrt(p.taa * tbb);
-    const double zncc = den > 0.0 ? tab / den : 0.0;
-    acc = ok ? acc + (1.0 - zncc) : acc;
-    valid += ok ? 1 : 0;
-  }
-  return (p.textured && valid >= c.min_views) ? acc / (double)valid : (double)INFINITY;
+__device__ __forceinline__ CostPixel pm_pixel(const PmTile<R>& t, int colour, const PmCost& c) {
+  const int ly = threadIdx.x >> 4, lx = 2 * (threadIdx.x & 15) + ((ly ^ colour) & 1);      // the tile's origin is even in x and y
+  return cost_pixel(t, lx, ly, c.H, c.W, c.min_variance);
 }
 
 // -------------------------------------------------------------------------------------------------------------- cost
@@ -171,12 +55,13 @@ __device__ __forceinline__ double pm_cost(const PmTile<R>& t, const PmPixel& p, 
 template <int R>
 __global__ __launch_bounds__(256) void pm_cost_kernel(const float* __restrict__ frames, const double* __restrict__ poses,
                                                      const double* __restrict__ cams, const double* __restrict__ rays,
-                                                     PmViews views, PmCost c, const double* __restrict__ plane,
+                                                     DenseViews views, PmCost c, const double* __restrict__ plane,
                                                      double* __restrict__ cost) {
   __shared__ PmTile<R> t;
-  pm_stage<R>(t, frames, poses, cams, rays, c.H, c.W, views);
-  const PmPixel p = pm_pixel<R>(t, (int)blockIdx.z, c.H, c.W, c.min_variance);
-  const double value = pm_cost<R>(t, p, frames, views, c, plane[3 * p.pix], plane[3 * p.pix + 1], plane[3 * p.pix + 2]);
+  cost_stage(t, frames, poses, cams, rays, c.H, c.W, views);
+  const CostPixel p = pm_pixel<R>(t, (int)blockIdx.z, c);
+  const Slanted own = {plane[3 * p.pix], plane[3 * p.pix + 1], plane[3 * p.pix + 2]};
+  const double value = window_cost(t, p, frames, views, c.H, c.W, c.min_views, own);
   if (p.stored) cost[p.pix] = value;
 }
 
@@ -193,10 +78,10 @@ struct PmStep {
 template <int R>
 __global__ __launch_bounds__(256) void pm_step_kernel(const float* __restrict__ frames, const double* __restrict__ poses,
                                                      const double* __restrict__ cams, const double* __restrict__ rays,
-                                                     PmViews views, PmCost c, PmStep s, double* plane, double* cost) {
+                                                     DenseViews views, PmCost c, PmStep s, double* plane, double* cost) {
   __shared__ PmTile<R> t;
-  pm_stage<R>(t, frames, poses, cams, rays, c.H, c.W, views);
-  const PmPixel p = pm_pixel<R>(t, s.colour, c.H, c.W, c.min_variance);
+  cost_stage(t, frames, poses, cams, rays, c.H, c.W, views);
+  const CostPixel p = pm_pixel<R>(t, s.colour, c);
   const int H = c.H, W = c.W;
   const double u0 = t.ray[p.centre][0], v0 = t.ray[p.centre][1];
   double al = plane[3 * p.pix], be = plane[3 * p.pix + 1], ga = plane[3 * p.pix + 2];
@@ -226,7 +111,7 @@ __global__ __launch_bounds__(256) void pm_step_kernel(const float* __restrict__ 
     }
     const bool legal = use && pm_legal(ca, cb, cg, u0, v0, s.w_far, s.w_near, s.cos_tilt);
     if (__ballot(legal) == 0ull) continue;              // wave-uniform
-    const double value = pm_cost<R>(t, p, frames, views, c, ca, cb, cg);
+    const double value = window_cost(t, p, frames, views, H, W, c.min_views, Slanted{ca, cb, cg});
     const bool better = legal && value < best;
     al = better ? ca : al;
     be = better ? cb : be;
@@ -304,19 +189,11 @@ static bool range_ok(double w_far, double w_near, double cos_tilt) {
   return w_far > 0.0 && w_far < w_near && isfinite(w_near) && cos_tilt >= 0.0 && cos_tilt <= 1.0;
 }
 
-// the views of a call from its host array; false: refused
-static bool make_views(int num_frames, int ref, const int32_t* sources, int num_sources, int radius, int min_views, PmViews* v) {
-  if (!sources || num_sources < 1 || num_sources > kMaxSources || radius < 1 || radius > VGGR_MAX_RADIUS || min_views < 1 ||
-      min_views > num_sources)
-    return false;
-  memset(v, 0, sizeof(*v));
-  v->ref = ref;
-  v->count = num_sources;
-  for (int m = 0; m < num_sources; ++m) {
-    if (sources[m] < 0 || sources[m] >= num_frames || sources[m] == ref) return false;
-    v->src[m] = sources[m];
-  }
-  return true;
+// the views of a call and the window's limits; false: refused
+static bool window_ok(int num_frames, int ref, const int32_t* sources, int num_sources, int radius, int min_views,
+                      DenseViews* v) {
+  return make_views(num_frames, ref, sources, num_sources, 1, nullptr, 0, v) && radius >= 1 && radius <= VGGR_MAX_RADIUS &&
+         min_views >= 1 && min_views <= num_sources;
 }
 
 static bool size_ok(int height, int width) {
@@ -349,8 +226,8 @@ int vggr_plane_init(const float* depth, const float* normals, const double* pose
 int vggr_plane_cost(const float* frames, const double* poses, const double* cams, const double* rays, int num_frames,
                     int height, int width, int ref, const int32_t* sources, int num_sources, int radius, int min_views,
                     double min_variance, const double* plane, double* cost, void* stream) {
-  PmViews views;
-  if (!frame_ok(num_frames, height, width, ref) || !make_views(num_frames, ref, sources, num_sources, radius, min_views, &views))
+  DenseViews views;
+  if (!frame_ok(num_frames, height, width, ref) || !window_ok(num_frames, ref, sources, num_sources, radius, min_views, &views))
     return VGG_ERR_INVALID_ARGUMENT;
   if (height == 0 || width == 0) return VGG_OK;
   if (!frames || !poses || !cams || !rays || !plane || !cost) return VGG_ERR_INVALID_ARGUMENT;
@@ -369,8 +246,8 @@ int vggr_step(const float* frames, const double* poses, const double* cams, cons
               int width, int ref, const int32_t* sources, int num_sources, int radius, int min_views, double min_variance,
               double inv_depth_far, double inv_depth_near, double depth_step, double slope_step, double cos_max_tilt,
               unsigned long long seed, int iteration, int colour, double* plane, double* cost, void* stream) {
-  PmViews views;
-  if (!frame_ok(num_frames, height, width, ref) || !make_views(num_frames, ref, sources, num_sources, radius, min_views, &views) ||
+  DenseViews views;
+  if (!frame_ok(num_frames, height, width, ref) || !window_ok(num_frames, ref, sources, num_sources, radius, min_views, &views) ||
       !range_ok(inv_depth_far, inv_depth_near, cos_max_tilt))
     return VGG_ERR_INVALID_ARGUMENT;
   if (colour < 0 || colour > 1 || iteration < 0 || !(depth_step >= 0.0) || !(slope_step >= 0.0) || !isfinite(depth_step) ||

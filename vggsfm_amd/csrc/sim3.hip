@@ -17,6 +17,7 @@
 #include "common.hpp"
 #include "jacobi.hpp"
 #include "kabsch3.hpp"
+#include "mvs/mvs_geometry.hpp"
 #include "support.hpp"
 #include "../../include/vggsfm_amd_sim3.h"
 
@@ -483,15 +484,7 @@ __global__ __launch_bounds__(256) void sim3_clear_failed_kernel(int N, const int
 }
 
 // ------------------------------------------------------------------------------------------------------ pair errors
-__device__ __forceinline__ void relative_pose(const double* Pi, const double* Pj, double* R, double* t) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = (Pj[4 * r] * Pi[4 * c] + Pj[4 * r + 1] * Pi[4 * c + 1]) + Pj[4 * r + 2] * Pi[4 * c + 2];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) t[r] = Pj[4 * r + 3] - ((R[3 * r] * Pi[3] + R[3 * r + 1] * Pi[7]) + R[3 * r + 2] * Pi[11]);
-}
-
+// (relative_pose, [R|t] of view j from view i as 3 x 4: mvs/mvs_geometry.hpp)
 __global__ __launch_bounds__(256) void pose_pair_errors_kernel(const double* __restrict__ pred, const double* __restrict__ gt, int S,
                                                                long pairs, double* __restrict__ out_rot, double* __restrict__ out_trans) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -503,16 +496,17 @@ __global__ __launch_bounds__(256) void pose_pair_errors_kernel(const double* __r
   while (i > 0 && i * (2L * S - i - 1) / 2 > p) --i;
   while (i < S - 2 && (i + 1) * (2L * S - i - 2) / 2 <= p) ++i;
   const long j = p - i * (2L * S - i - 1) / 2 + i + 1;
-  double Pi[12], Pj[12], Rg[9], tg[3], Rp[9], tp[3];
+  double Pi[12], Pj[12], Tg[12], Tp[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) { Pi[k] = gt[i * 12 + k]; Pj[k] = gt[j * 12 + k]; }
-  relative_pose(Pi, Pj, Rg, tg);
+  relative_pose(Pi, Pj, Tg);
 #pragma unroll
   for (int k = 0; k < 12; ++k) { Pi[k] = pred[i * 12 + k]; Pj[k] = pred[j * 12 + k]; }
-  relative_pose(Pi, Pj, Rp, tp);
+  relative_pose(Pi, Pj, Tp);
   double tr = 0.0;
 #pragma unroll
-  for (int k = 0; k < 9; ++k) tr = tr + Rg[k] * Rp[k];
+  for (int k = 0; k < 9; ++k) tr = tr + Tg[4 * (k / 3) + k % 3] * Tp[4 * (k / 3) + k % 3];
+  const double tg[3] = {Tg[3], Tg[7], Tg[11]}, tp[3] = {Tp[3], Tp[7], Tp[11]};
   const double d2 = (1.0 + tr) * 0.25;
   const double loss_q = fmax(1.0 - d2, kAngleEps);
   out_rot[p] = acos(1.0 - 2.0 * loss_q) * kDegrees;

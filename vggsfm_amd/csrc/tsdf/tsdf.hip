@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include "../common.hpp"
+#include "../scan.hpp"
 #include "../mvs/mvs_geometry.hpp"
 #include "vggsfm_amd_tsdf.h"
 
@@ -56,28 +57,6 @@ __device__ __forceinline__ bool node_value(const double* __restrict__ tsdf, cons
   const double w = wsum[n];
   s = tsdf[n] / w;
   return w >= min_weight;
-}
-
-// exclusive prefix of v over the workgroup in thread order; *total = the sum
-template <int WAVES>
-__device__ __forceinline__ int block_scan_int(int v, int* wave_tot, int* total) {
-  const int lane = lane_id(), w = threadIdx.x / kWave;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int y = __shfl_up(x, d, kWave);
-    if (lane >= d) x += y;
-  }
-  if (lane == kWave - 1) wave_tot[w] = x;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < WAVES; ++k) {
-    before += k < w ? wave_tot[k] : 0;
-    all += wave_tot[k];
-  }
-  *total = all;
-  return before + x - v;
 }
 
 // ------------------------------------------------------------------------------------------------------- integration

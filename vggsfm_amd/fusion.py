@@ -22,47 +22,12 @@ from ._lib_fuse import check, require_gpu, stream_ptr
 
 _L = F.lib()          # no fallback: importing the fusion without its library is an error
 
+# (below the load: without the library, importing this module fails with lib()'s error whatever else is missing)
+from ._dense_args import all_view_inputs, host_i32  # noqa: E402
+
 FusedCloud = namedtuple("FusedCloud", "xyz normal rgb num_views view pixel")
 
 _AUTO = "auto"
-
-
-def _host_i32(values):
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(values, dtype=np.int64).reshape(-1).astype(np.int32)))
-
-
-def _f64(t, shape, what):
-    t = torch.as_tensor(t)
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.to(torch.float64).contiguous()
-
-
-def _inputs(depth, poses, cams, rays, ray_index):
-    """the checked device tensors every entry takes: depth, poses, cams, rays, host ray_index"""
-    from .mvs import camera_rays
-
-    depth = torch.as_tensor(depth)
-    if depth.dim() != 3 or depth.dtype != torch.float32:
-        raise ValueError(f"depth must be (S,H,W) float32, got {tuple(depth.shape)} {depth.dtype}")
-    depth = depth.contiguous()
-    require_gpu(depth)
-    S, H, W = depth.shape
-    dev = depth.device
-    poses, cams = _f64(poses, (S, 3, 4), "poses").to(dev), _f64(cams, (S, 4), "cams").to(dev)
-    if rays is None:
-        rays, ray_index = camera_rays(cams, H, W, dev)
-    rays = torch.as_tensor(rays)
-    if rays.dim() != 4:
-        raise ValueError(f"rays must be (NR,H,W,2), got {tuple(rays.shape)}")
-    rays = _f64(rays, (rays.shape[0], H, W, 2), "rays")
-    require_gpu(rays)
-    if ray_index is None:
-        raise ValueError("rays without ray_index")
-    ridx = _host_i32(ray_index)
-    if ridx.numel() != S:
-        raise ValueError(f"ray_index must have {S} entries, got {ridx.numel()}")
-    return depth, poses, cams, rays, ridx
 
 
 def depth_normals(depth, poses, cams, max_rel_jump=0.05, rays=None, ray_index=None):
@@ -71,7 +36,7 @@ def depth_normals(depth, poses, cams, max_rel_jump=0.05, rays=None, ray_index=No
     neighbours' camera-frame points; a neighbour counts when its depth differs by at most max_rel_jump of the pixel's.
     (0, 0, 0) where there is none.  rays (NR,H,W,2) and ray_index (S,): the ray maps and which one a view uses (default:
     mvs.camera_rays(cams)).  What the entry refuses (vggsfm_amd_fuse.h) raises RuntimeError."""
-    depth, poses, cams, rays, ridx = _inputs(depth, poses, cams, rays, ray_index)
+    depth, poses, cams, rays, ridx = all_view_inputs(depth, poses, cams, rays, ray_index)
     S, H, W = depth.shape
     out = torch.empty(S, H, W, 3, dtype=torch.float32, device=depth.device)
     check(_L.vggf_depth_normals(depth, poses, rays, ridx, rays.shape[0], S, H, W, max_rel_jump, out, stream_ptr()),
@@ -95,7 +60,7 @@ def fuse_depth_maps(depth, poses, cams, sources, colors=None, normals=_AUTO, rel
     (S,H,W,3) float32 tensor, or None: no normal test and normal is (N,3) zeros.  A view of view_order with fewer than
     min_views - 1 sources is refused, as is everything else the entry refuses (vggsfm_amd_fuse.h): RuntimeError.
     return_claimed: also return the (S,H,W) uint8 map of the claimed pixels."""
-    depth, poses, cams, rays, ridx = _inputs(depth, poses, cams, rays, ray_index)
+    depth, poses, cams, rays, ridx = all_view_inputs(depth, poses, cams, rays, ray_index)
     S, H, W = depth.shape
     dev = depth.device
     if len(sources) != S:
@@ -121,7 +86,7 @@ def fuse_depth_maps(depth, poses, cams, sources, colors=None, normals=_AUTO, rel
             raise ValueError(f"colors must be {(S, 3, H, W)} float32, got {tuple(colors.shape)} {colors.dtype}")
         colors = colors.contiguous()
         require_gpu(colors)
-    src = [_host_i32(s) for s in sources]
+    src = [host_i32(s) for s in sources]
     plane = H * W
     # a point is a pixel with depth: one host read sizes the outputs
     capacity = int((depth[torch.as_tensor(order, dtype=torch.long, device=dev)] > 0).sum()) if order and plane else 0

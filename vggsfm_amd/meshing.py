@@ -20,7 +20,8 @@ import torch
 
 from . import _lib_tsdf as T
 from ._lib_tsdf import check, require_gpu, stream_ptr
-from .fusion import _PLY_NAMES, _f64, _host
+from ._dense_args import f64, maps
+from .fusion import _PLY_NAMES, _host
 
 _L = T.lib()          # no fallback: importing the meshing without its library is an error
 
@@ -76,16 +77,12 @@ class TSDFVolume:
         with weight 0 adds nothing.  frames (S,3,H,W) float32 planar colours or None (a volume with colour then keeps what
         it has).  trunc defaults to 4 voxels -- a default, not a tuned value: it must exceed the noise of the maps and
         stay below the thinnest structure.  Returns self."""
-        depth = torch.as_tensor(depth)
-        if depth.dim() != 3 or depth.dtype != torch.float32:
-            raise ValueError(f"depth must be (S,H,W) float32, got {tuple(depth.shape)} {depth.dtype}")
-        depth = depth.contiguous()
-        require_gpu(depth)
+        depth = maps(depth, "depth")
         S, H, W = depth.shape
         if S < 1:
             raise ValueError("no view to integrate")
         dev = self.tsdf_sum.device
-        poses, cams = _f64(poses, (S, 3, 4), "poses").to(dev), _f64(cams, (S, 4), "cams").to(dev)
+        poses, cams = f64(poses, (S, 3, 4), "poses").to(dev), f64(cams, (S, 4), "cams").to(dev)
         trunc = 4.0 * self.voxel if trunc is None else float(trunc)
         if not trunc > 0.0:
             raise ValueError(f"trunc must be > 0, got {trunc}")

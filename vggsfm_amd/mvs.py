@@ -21,28 +21,14 @@ from ._lib_mvs import check, require_gpu, stream_ptr
 
 _L = M.lib()          # no fallback: importing the stereo without its library is an error
 
+# (below the load: without the library, importing this module fails with lib()'s error whatever else is missing)
+from ._dense_args import all_view_inputs, host_i32, reference_inputs  # noqa: E402
+
 Sweep = namedtuple("Sweep", "depth conf index cost")
 Filtered = namedtuple("Filtered", "depth count")
 
 RANGE_PERCENTILES = (5.0, 95.0)   # depth_ranges: percentiles of the sparse depths ...
 RANGE_WIDEN = 1.25                # ... near divided, far multiplied by this factor
-
-
-def _host_i32(values):
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(values, dtype=np.int64).reshape(-1).astype(np.int32)))
-
-
-def _f64(t, shape, what):
-    t = torch.as_tensor(t)
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.to(torch.float64).contiguous()
-
-
-def _maps(t, what):
-    if t.dim() != 3 or t.dtype != torch.float32:
-        raise ValueError(f"{what} must be (S,H,W) float32, got {tuple(t.shape)} {t.dtype}")
-    return t.contiguous()
 
 
 def pixel_rays(cam_row, height, width, device=None):
@@ -72,7 +58,7 @@ def camera_rays(cams, height, width, device=None):
             seen[key] = len(maps)
             maps.append(pixel_rays(row, height, width, device))
         index.append(seen[key])
-    return torch.stack(maps), _host_i32(index)
+    return torch.stack(maps), host_i32(index)
 
 
 def plane_sweep(frames, poses, cams, ref, sources, depth_near, depth_far, num_planes=128, radius=2, min_views=1,
@@ -81,20 +67,12 @@ def plane_sweep(frames, poses, cams, ref, sources, depth_near, depth_far, num_pl
     int32, cost (D,H,W) float64 or None) of view `ref` against `sources` (1 .. 8 other views), planes uniform in inverse
     depth between depth_far and depth_near.  rays: the ray map of view ref (default: pixel_rays of its camera).  What the
     entry refuses (vggsfm_amd_mvs.h) raises RuntimeError."""
-    frames = _maps(frames, "frames")
-    require_gpu(frames)
+    frames, poses, cams, rays = reference_inputs(frames, poses, cams, ref, rays)
     S, H, W = frames.shape
     dev = frames.device
-    poses, cams = _f64(poses, (S, 3, 4), "poses").to(dev), _f64(cams, (S, 4), "cams").to(dev)
     if not (depth_near > 0 and depth_far > 0 and np.isfinite(depth_near) and np.isfinite(depth_far)):
         raise ValueError(f"depth_near and depth_far must be positive and finite, got {depth_near} and {depth_far}")
-    if rays is None:
-        if not 0 <= ref < S:
-            raise ValueError(f"ref {ref} outside [0, {S})")
-        rays = pixel_rays(cams[ref], H, W, dev)
-    rays = _f64(rays, (H, W, 2), "rays")
-    require_gpu(rays)
-    src = _host_i32(sources)
+    src = host_i32(sources)
     depth = torch.empty(H, W, dtype=torch.float32, device=dev)
     conf = torch.empty(H, W, dtype=torch.float32, device=dev)
     index = torch.empty(H, W, dtype=torch.int32, device=dev)
@@ -110,21 +88,10 @@ def filter_consistent(depth, poses, cams, ref, sources, rel_depth_tol=0.01, repr
     """depth (S,H,W) float32 (0: none), poses (S,3,4), cams (S,4) -> Filtered(depth (H,W) float32, count (H,W) int32): the
     depth of view `ref` where at least min_consistent of `sources` confirm it forwards and backwards.  rays (NR,H,W,2) and
     ray_index (S,): the ray maps and which one a view uses (default: camera_rays(cams))."""
-    depth = _maps(depth, "depth")
-    require_gpu(depth)
+    depth, poses, cams, rays, ridx = all_view_inputs(depth, poses, cams, rays, ray_index)
     S, H, W = depth.shape
     dev = depth.device
-    poses, cams = _f64(poses, (S, 3, 4), "poses").to(dev), _f64(cams, (S, 4), "cams").to(dev)
-    if rays is None:
-        rays, ray_index = camera_rays(cams, H, W, dev)
-    if rays.dim() != 4:
-        raise ValueError(f"rays must be (NR,H,W,2), got {tuple(rays.shape)}")
-    rays = _f64(rays, (rays.shape[0], H, W, 2), "rays")
-    require_gpu(rays)
-    ridx = _host_i32(ray_index)
-    if ridx.numel() != S:
-        raise ValueError(f"ray_index must have {S} entries, got {ridx.numel()}")
-    src = _host_i32(sources)
+    src = host_i32(sources)
     out = torch.empty(H, W, dtype=torch.float32, device=dev)
     count = torch.empty(H, W, dtype=torch.int32, device=dev)
     check(_L.vggm_consistency_filter(depth, poses, cams, rays, ridx, rays.shape[0], S, H, W, ref, src, src.numel(),

@@ -23,27 +23,11 @@ import torch
 from . import _lib_patchmatch as PM
 from . import mvs
 from ._lib_patchmatch import check, require_gpu, stream_ptr
-from .mvs import _f64, _host_i32, _maps
+from ._dense_args import f64, host_i32, reference_inputs
 
 _L = PM.lib()         # no fallback: importing the refinement without its library is an error
 
 Refined = namedtuple("Refined", "depth conf normal plane cost")
-
-
-def _views(frames, poses, cams, ref, rays):
-    """the checked device tensors every entry takes"""
-    frames = _maps(frames, "frames")
-    require_gpu(frames)
-    S, H, W = frames.shape
-    dev = frames.device
-    poses, cams = _f64(poses, (S, 3, 4), "poses").to(dev), _f64(cams, (S, 4), "cams").to(dev)
-    if rays is None:
-        if not 0 <= ref < S:
-            raise ValueError(f"ref {ref} outside [0, {S})")
-        rays = mvs.pixel_rays(cams[ref], H, W, dev)
-    rays = _f64(rays, (H, W, 2), "rays")
-    require_gpu(rays)
-    return frames, poses, cams, rays
 
 
 def _range(depth_near, depth_far):
@@ -96,7 +80,7 @@ def plane_init(depth, poses, ref, rays, depth_near, depth_far, normals=None, max
     if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
         raise ValueError(f"poses must be (S,3,4), got {tuple(poses.shape)}")
     poses = poses.to(torch.float64).contiguous().to(dev)
-    rays = _f64(rays, (H, W, 2), "rays")
+    rays = f64(rays, (H, W, 2), "rays")
     require_gpu(rays)
     if normals is not None:
         if tuple(normals.shape) != (H, W, 3) or normals.dtype != torch.float32:
@@ -114,10 +98,10 @@ def plane_cost(frames, poses, cams, ref, sources, plane, radius=2, min_views=1, 
     """frames (S,H,W) float32 grey, poses (S,3,4), cams (S,4), plane (H,W,3) float64 -> cost (H,W) float64: per pixel of view
     `ref` the sweep's cost (mean of 1 - ZNCC over the valid sources, +inf with fewer than min_views or too little variance)
     of that pixel's plane.  The plane (0, 0, w_j) gives the bits of mvs.plane_sweep(..., return_cost=True).cost[j]."""
-    frames, poses, cams, rays = _views(frames, poses, cams, ref, rays)
+    frames, poses, cams, rays = reference_inputs(frames, poses, cams, ref, rays)
     S, H, W = frames.shape
     plane = _state(plane, (H, W, 3), "plane", frames.device)
-    src = _host_i32(sources)
+    src = host_i32(sources)
     cost = torch.empty(H, W, dtype=torch.float64, device=frames.device)
     check(_L.vggr_plane_cost(frames, poses, cams, rays, S, H, W, ref, src, src.numel(), radius, min_views, min_variance, plane,
                              cost, stream_ptr()), "vggr_plane_cost")
@@ -128,12 +112,12 @@ def step(frames, poses, cams, ref, sources, plane, cost, depth_near, depth_far, 
          max_tilt_deg=75.0, radius=2, min_views=1, min_variance=1e-4, seed=0, rays=None):
     """One half-iteration on the pixels with (x + y) & 1 == colour: plane (H,W,3) and cost (H,W) float64 are updated in
     place (and returned).  Asynchronous."""
-    frames, poses, cams, rays = _views(frames, poses, cams, ref, rays)
+    frames, poses, cams, rays = reference_inputs(frames, poses, cams, ref, rays)
     S, H, W = frames.shape
     plane = _state(plane, (H, W, 3), "plane", frames.device)
     cost = _state(cost, (H, W), "cost", frames.device)
     w_far, w_near = _range(depth_near, depth_far)
-    src = _host_i32(sources)
+    src = host_i32(sources)
     check(_L.vggr_step(frames, poses, cams, rays, S, H, W, ref, src, src.numel(), radius, min_views, min_variance, w_far, w_near,
                        depth_step, slope_step, tilt_cos(max_tilt_deg), _seed(seed), iteration, colour, plane, cost, stream_ptr()),
           "vggr_step")
@@ -154,7 +138,7 @@ def outputs(plane, cost, poses, ref, rays, min_conf=0.5):
     if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
         raise ValueError(f"poses must be (S,3,4), got {tuple(poses.shape)}")
     poses = poses.to(torch.float64).contiguous().to(dev)
-    rays = _f64(rays, (H, W, 2), "rays")
+    rays = f64(rays, (H, W, 2), "rays")
     require_gpu(rays)
     depth = torch.empty(H, W, dtype=torch.float32, device=dev)
     conf = torch.empty(H, W, dtype=torch.float32, device=dev)
@@ -176,7 +160,7 @@ def refine_depth(frames, poses, cams, ref, sources, depth_near, depth_far, init_
     scale of the inverse-depth perturbation (default: two plane spacings of a sweep of num_planes planes); slope_step: that
     of the slopes, relative to the pixel's inverse depth; max_tilt_deg: the largest angle between a plane's normal and the
     pixel's ray.  iterations = 0 returns the start.  What the entries refuse (vggsfm_amd_patchmatch.h) raises RuntimeError."""
-    frames, poses, cams, rays = _views(frames, poses, cams, ref, rays)
+    frames, poses, cams, rays = reference_inputs(frames, poses, cams, ref, rays)
     if iterations < 0:
         raise ValueError(f"iterations must be >= 0, got {iterations}")
     if init_depth is None:
