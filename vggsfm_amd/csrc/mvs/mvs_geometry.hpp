@@ -1,7 +1,7 @@
 // The pose, transfer and projection arithmetic that vggsfm_amd_mvs.h states under "Shared by both entries" and the sweep's
 // bilinear sample: one copy, included (directly or through mvs_views.hpp and mvs_cost.hpp) by mvs.hip, ../fuse/fuse.hip,
-// ../patchmatch/patchmatch.hip, ../tsdf/tsdf.hip, ../klt/klt.hip and ../sim3.hip (all parity files, built with
-// -ffp-contract=off).
+// ../patchmatch/patchmatch.hip, ../tsdf/tsdf.hip, ../raster/raster.hip, ../klt/klt.hip and ../sim3.hip (all parity files,
+// built with -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,17 +19,27 @@ __device__ __forceinline__ void relative_pose(const double* __restrict__ pa, con
   }
 }
 
-// transfer P by T = [R|t] and project with cam = f, cx, cy, k; false: behind the camera (x, y are then not to be used)
-__device__ __forceinline__ bool transfer_project(const double* T, const double* cam, double p0, double p1, double p2, double& x,
-                                                 double& y, double& z) {
-  const double X0 = T[0] * p0 + T[1] * p1 + T[2] * p2 + T[3];
-  const double X1 = T[4] * p0 + T[5] * p1 + T[6] * p2 + T[7];
-  const double X2 = T[8] * p0 + T[9] * p1 + T[10] * p2 + T[11];
-  const double iz = 1.0 / X2;
-  const double a = X0 * iz, b = X1 * iz;
+// transfer P by T = [R|t]
+__device__ __forceinline__ void transfer(const double* T, double p0, double p1, double p2, double& X0, double& X1, double& X2) {
+  X0 = T[0] * p0 + T[1] * p1 + T[2] * p2 + T[3];
+  X1 = T[4] * p0 + T[5] * p1 + T[6] * p2 + T[7];
+  X2 = T[8] * p0 + T[9] * p1 + T[10] * p2 + T[11];
+}
+
+// the pixel of the normalised image point (a, b) under cam = f, cx, cy, k
+__device__ __forceinline__ void project_normalised(const double* cam, double a, double b, double& x, double& y) {
   const double d = 1.0 + cam[3] * (a * a + b * b);
   x = cam[0] * (a * d) + cam[1];
   y = cam[0] * (b * d) + cam[2];
+}
+
+// transfer P by T = [R|t] and project with cam = f, cx, cy, k; false: behind the camera (x, y are then not to be used)
+__device__ __forceinline__ bool transfer_project(const double* T, const double* cam, double p0, double p1, double p2, double& x,
+                                                 double& y, double& z) {
+  double X0, X1, X2;
+  transfer(T, p0, p1, p2, X0, X1, X2);
+  const double iz = 1.0 / X2;
+  project_normalised(cam, X0 * iz, X1 * iz, x, y);
   z = X2;
   return X2 > 0.0;
 }

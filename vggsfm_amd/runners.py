@@ -342,6 +342,21 @@ class GeometryRunner:
             meshing.write_mesh_ply(output_path, mesh)
         return predictions
 
+    # ------------------------------------------------------------------ the surface seen from the cameras
+    def render_dense_mesh(self, predictions, **options):
+        """predictions["dense_mesh"] (of mesh_dense_surface) rendered into every registered image of
+        predictions["reconstruction"] through a z-buffer (vggsfm_amd.render, `options` are render_reconstruction's).  Sets
+        predictions["mesh_depth_dict"] ((H,W) float32 device tensors by image name, 0 = none: hole-free wherever the mesh
+        is, and occlusion-correct), ["mesh_normal_dict"] and ["mesh_rgb_dict"] ((H,W,3) float32: the mesh's unit world
+        normals and colours, zeros = none) -- the shapes depth_dict and depth_normal_dict use.  No other key changes."""
+        from . import render
+
+        depth, normal, rgb, _ = render.render_reconstruction(predictions["reconstruction"], predictions["dense_mesh"], **options)
+        predictions["mesh_depth_dict"] = depth
+        predictions["mesh_normal_dict"] = normal
+        predictions["mesh_rgb_dict"] = rgb
+        return predictions
+
     # ------------------------------------------------------------------ track video (runner.py:445-450)
     def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
         """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
