@@ -357,6 +357,20 @@ class GeometryRunner:
         predictions["mesh_rgb_dict"] = rgb
         return predictions
 
+    # ------------------------------------------------------------------ the dense model against a reference
+    def evaluate_dense_model(self, predictions, reference, thresholds, max_dist, which="fused_point_cloud", transform=None):
+        """How far predictions[which] -- "fused_point_cloud" (of fuse_dense_point_cloud) or "dense_mesh" (of
+        mesh_dense_surface) -- is from `reference` (a point set (N,3), a fusion.FusedCloud or a meshing.Mesh in the same
+        gauge, or in the gauge that `transform` = (scale, R, t) of vggsfm_amd.sim3 takes the prediction to): accuracy,
+        completeness and, per threshold, precision, recall and F-score within max_dist (vggsfm_amd.utils.dense_metric).
+        Sets predictions["dense_metrics"], a dict of Python numbers.  No other key changes."""
+        from .utils import dense_metric
+
+        if which not in ("fused_point_cloud", "dense_mesh"):
+            raise ValueError(f"which must be 'fused_point_cloud' or 'dense_mesh', got {which!r}")
+        predictions["dense_metrics"] = dense_metric.evaluate_dense(predictions[which], reference, thresholds, max_dist, transform)
+        return predictions
+
     # ------------------------------------------------------------------ track video (runner.py:445-450)
     def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
         """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
