@@ -5,17 +5,20 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 COMMON = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno-unused-function
 # the library's own header and the headers the side libraries share
-HDRS = $(HEADER) ../common.hpp ../crosslane.hpp ../scan.hpp $(wildcard ../mvs/*.hpp)
-OBJ = _obj/$(basename $(SRC)).o
+HDRS = $(HEADER) ../common.hpp ../crosslane.hpp ../scan.hpp ../jacobi.hpp $(wildcard ../mvs/*.hpp) $(wildcard ../nn/*.hpp)
+# (OBJDIR and EXTRA: a measurement build of the same recipe with other constants, e.g. scripts/time_icp.py)
+OBJDIR ?= _obj
+EXTRA ?=
+OBJ = $(OBJDIR)/$(basename $(SRC)).o
 
 all: $(OUT)
 
 $(OBJ): $(SRC) $(HDRS)
-	@mkdir -p _obj
-	$(HIPCC) $(COMMON) -ffp-contract=off -c $< -o $@
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(COMMON) $(EXTRA) -ffp-contract=off -c $< -o $@
 
 $(OUT): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ)
 
 clean:
-	rm -rf _obj $(OUT)
+	rm -rf $(OBJDIR) $(OUT)

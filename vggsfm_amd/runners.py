@@ -371,6 +371,33 @@ class GeometryRunner:
         predictions["dense_metrics"] = dense_metric.evaluate_dense(predictions[which], reference, thresholds, max_dist, transform)
         return predictions
 
+    # ------------------------------------------------------------------ the dense model registered to a reference
+    def register_dense_model(self, predictions, reference, max_dist, which="fused_point_cloud", init=None, **options):
+        """predictions[which] -- "fused_point_cloud" or "dense_mesh" (its vertices) -- registered to `reference` (a point
+        set (N,3), a fusion.FusedCloud, a meshing.Mesh or a registration.Target) by ICP on the dense geometry
+        (vggsfm_amd.registration.icp, `options` are its keywords; max_dist a number or coarse-to-fine stages; init = (scale,
+        R, t), e.g. of sim3.align_cameras).  A point set without normals gets them estimated within normal_radius (default:
+        twice the last max_dist) unless metric="point_to_point".  Sets predictions["dense_registration"]: scale, R, t,
+        transform = (scale, R, t) as device tensors, the tuple evaluate_dense_model(transform=...) takes, status, iterations,
+        rmse, fitness.  No other key changes."""
+        from . import registration
+
+        if which not in ("fused_point_cloud", "dense_mesh"):
+            raise ValueError(f"which must be 'fused_point_cloud' or 'dense_mesh', got {which!r}")
+        stages = list(max_dist) if isinstance(max_dist, (list, tuple)) else [max_dist]
+        normal_radius = options.pop("normal_radius", 2.0 * float(stages[-1]))
+        if options.get("metric", "point_to_plane") == "point_to_point":
+            normal_radius = None
+        cell = options.get("cell") or float(stages[0])
+        target = reference if isinstance(reference, registration.Target) else registration.make_target(reference, cell, normal_radius)
+        model = predictions[which]
+        reg = registration.icp(model, target, max_dist, init=init, **options)
+        dev = target.grid.device
+        transform = (torch.tensor(reg.scale, dtype=torch.float64, device=dev), reg.R.to(dev), reg.t.to(dev))
+        predictions["dense_registration"] = {"scale": reg.scale, "R": reg.R, "t": reg.t, "transform": transform, "status": reg.status,
+                                             "iterations": reg.iterations, "rmse": reg.rmse, "fitness": reg.fitness}
+        return predictions
+
     # ------------------------------------------------------------------ track video (runner.py:445-450)
     def visualize_tracks(self, images, pred_track, pred_vis, output_dir=None):
         """runner.py:445-450 (cfg.visual_tracks): the tracker's raw predictions drawn over the frames, on the device
