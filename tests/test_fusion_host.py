@@ -1,7 +1,8 @@
-"""CPU tests of the depth-map fusion: its C-ABI registry (vggsfm_amd/_lib_fuse.py against csrc/fuse/vggsfm_amd_fuse.h and the
-dynamic symbols of libvggsfm_amd_fuse.so), what the entries refuse, the yardstick of the GPU tests (the NumPy restatement
-of tests/fusion_cases.py) against analytic truth, the de-duplication as a condition, the margins of every decision the GPU
-tests compare exactly, the PLY round trip, and the loud failure without the library.  No kernel is called here."""
+"""CPU tests of the depth-map fusion: what its C-ABI registry has of its own (the registry itself is
+tests/test_side_libraries.py's), what the entries refuse, the yardstick of the GPU tests (the NumPy restatement of
+tests/fusion_cases.py) against analytic truth, the de-duplication as a condition, the margins of every decision the GPU tests
+compare exactly, the PLY round trip, and the loud failure of the product module without the library.  No kernel is called
+here."""
 import os
 import re
 import subprocess
@@ -11,54 +12,25 @@ import numpy as np
 import pytest
 
 from tests import fusion_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_fuse, _lib_klt, _lib_mvs, _lib_selftest
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_fuse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHERS = (_lib, _lib_klt, _lib_mvs, _lib_selftest)
-
-
-def _symbols(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r" T (vgg[a-z]*_\w+)$", nm, flags=re.M))
+NAMES = ["vggf_build_arch", "vggf_depth_normals", "vggf_fuse_view"]
 
 
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix, disjoint from the other four libraries'; the header beside the source, not under include/."""
+    """What only the fusion has (tests/test_side_libraries.py compares table, header and symbols): the names and prototypes
+    pinned by hand, and the header's constant against the binding and the restatement."""
     header = open(_lib_fuse.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_fuse.SIGNATURES)
-    assert list(table) == list(functions) == ["vggf_build_arch", "vggf_depth_normals", "vggf_fuse_view"] and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggf_"), name
+    functions, _ = _parse_header(header)
+    assert list(_lib_fuse.SIGNATURES) == list(functions) == NAMES
     assert functions["vggf_build_arch"] == ("pointer", [])
     assert functions["vggf_depth_normals"][1] == ["pointer"] * 4 + ["int"] * 4 + ["double", "pointer", "pointer"]
     assert functions["vggf_fuse_view"][1][7:18] == ["int"] * 5 + ["pointer", "int", "double", "double", "double", "int"]
     assert functions["vggf_fuse_view"][1][26] == "long" and len(functions["vggf_fuse_view"][1]) == 34
-    assert os.path.exists(_lib_fuse.LIB_PATH), "run __graft_entry__.build() first"
-    assert _symbols(_lib_fuse.LIB_PATH) == set(_lib_fuse.SIGNATURES)
-    prefixes = set()
-    for other in OTHERS:
-        assert not set(_lib_fuse.SIGNATURES) & set(other.SIGNATURES)
-        prefixes |= {n[:n.index("_") + 1] for n in other.SIGNATURES}
-    assert "vggf_" not in prefixes and {"vgg_", "vggk_", "vggm_", "vggs_"} <= prefixes
-    assert _lib_fuse.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_fuse.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "fuse")
-    L = _lib_fuse.lib()
-    assert L.vggf_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_fuse.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGF_(\w+) (\d+)", header))
-    assert int(consts["MAX_SOURCES"]) == _lib_fuse.MAX_SOURCES == C.MAX_SOURCES == _lib_mvs.MAX_SOURCES
-
-
-def test_the_other_libraries_keep_their_symbols():
-    """The fusion's translation unit is in none of the other four libraries: each exports exactly its table."""
-    for other in OTHERS:
-        assert _symbols(other.LIB_PATH) == set(other.SIGNATURES), other.LIB_PATH
+    assert int(consts["MAX_SOURCES"]) == _lib_fuse.MAX_SOURCES == C.MAX_SOURCES         # (and the stereo's: test_side_libraries.py)
 
 
 def test_host_refusals_need_no_device():

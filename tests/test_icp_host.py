@@ -1,42 +1,31 @@
-"""CPU tests of the registration library: its C-ABI registry (vggsfm_amd/_lib_icp.py against csrc/icp/vggsfm_amd_icp.h and the
-dynamic symbols of libvggsfm_amd_icp.so), what the entries refuse, the loud failure without the library, and the yardstick of
-the GPU tests (the all-pairs NumPy restatement of tests/icp_cases.py) against independent answers: torch-autograd's gradient
-and Gauss-Newton matrix, scipy's k-d tree, recovery of a known transform, the analytic normals of the base scene; and the
-margins of every decision the GPU tests compare exactly.  No kernel is called here."""
+"""CPU tests of the registration library: what its C-ABI registry has of its own (the registry itself is
+tests/test_side_libraries.py's), the one copy of the grid walk, what the entries refuse, and the yardstick of the GPU tests
+(the all-pairs NumPy restatement of tests/icp_cases.py) against independent answers: torch-autograd's gradient and
+Gauss-Newton matrix, scipy's k-d tree, recovery of a known transform, the analytic normals of the base scene; and the margins
+of every decision the GPU tests compare exactly.  No kernel is called here."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import icp_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import (_lib, _lib_fuse, _lib_icp, _lib_klt, _lib_mvs, _lib_nn, _lib_patchmatch, _lib_raster, _lib_selftest,
-                        _lib_tsdf)
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_icp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHERS = (_lib, _lib_klt, _lib_mvs, _lib_selftest, _lib_fuse, _lib_patchmatch, _lib_tsdf, _lib_raster, _lib_nn)
 NAMES = ["vggi_build_arch", "vggi_icp_step", "vggi_icp_step_mesh", "vggi_icp_sums", "vggi_icp_update", "vggi_radius_normals"]
 GAP_FLOOR = 1e-9           # relative to r2; rounding differences would show at 1e-16
 EIGEN_GAP_FLOOR = 0.05
 
 
-def _symbols(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r" T (vgg[a-z]*_\w+)$", nm, flags=re.M))
-
-
 # --------------------------------------------------------------------------------------------------- registry
 def test_header_table_and_library_agree():
+    """What only the registration has (tests/test_side_libraries.py compares table, header and symbols): the names and
+    prototypes pinned by hand, the header's constants against the binding and the restatement, and the one grid walk."""
     header = open(_lib_icp.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_icp.SIGNATURES)
-    assert list(table) == list(functions) == NAMES and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggi_"), name
+    functions, _ = _parse_header(header)
+    assert list(_lib_icp.SIGNATURES) == list(functions) == NAMES
     grid = ["double"] * 4 + ["int"] * 3
     tail = ["pointer", "double", "double", "int", "int", "int", "double", "pointer", "pointer", "pointer"]
     assert functions["vggi_icp_step"] == ("int", ["pointer", "pointer", "int", "pointer", "pointer", "pointer", "int"] + grid + ["pointer"] + tail)
@@ -44,24 +33,6 @@ def test_header_table_and_library_agree():
                                                   "int"] + grid + tail
     assert functions["vggi_icp_update"][1] == ["pointer", "pointer", "int", "int"] + ["double"] * 4 + ["pointer", "int", "pointer"]
     assert functions["vggi_radius_normals"][1] == ["pointer"] * 3 + ["int"] + grid + ["double", "double", "int"] + ["pointer"] * 5
-    assert os.path.exists(_lib_icp.LIB_PATH), "run __graft_entry__.build() first"
-    assert _symbols(_lib_icp.LIB_PATH) == set(_lib_icp.SIGNATURES)
-    prefixes = set()
-    for other in OTHERS:
-        assert not set(_lib_icp.SIGNATURES) & set(other.SIGNATURES)
-        assert _symbols(other.LIB_PATH) == set(other.SIGNATURES), other.LIB_PATH       # the nine others export exactly their tables
-        prefixes |= {n[:n.index("_") + 1] for n in other.SIGNATURES}
-    assert "vggi_" not in prefixes and len(OTHERS) == 9
-    assert {"vgg_", "vggk_", "vggm_", "vggs_", "vggf_", "vggp_", "vggr_", "vggv_", "vggz_", "vggn_"} <= prefixes
-    for name in os.listdir(os.path.join(ROOT, "include")):
-        assert "vggi_" not in open(os.path.join(ROOT, "include", name)).read(), name
-    assert _lib_icp.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_icp.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "icp")
-    L = _lib_icp.lib()
-    assert L.vggi_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_icp.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGI_(\w+) ([\de.-]+)", header))
     assert {k: int(consts[k]) for k in ("GROUPS", "BLOCK", "WORDS", "STATE_WORDS", "HISTORY_WORDS", "NORMAL_SWEEPS")} == \
         dict(GROUPS=_lib_icp.GROUPS, BLOCK=_lib_icp.BLOCK, WORDS=_lib_icp.WORDS, STATE_WORDS=_lib_icp.STATE_WORDS,
@@ -70,10 +41,6 @@ def test_header_table_and_library_agree():
     assert (C.GROUPS, C.BLOCK, C.WORDS) == (_lib_icp.GROUPS, _lib_icp.BLOCK, _lib_icp.WORDS)
     assert [int(consts[k]) for k in ("RUNNING", "CONVERGED", "TOO_FEW", "DEGENERATE")] == [0, 1, 2, 3]
     assert _lib_icp.STATUS == C.STATUS == ("running", "converged", "too few", "degenerate")
-    import __graft_entry__ as G
-    assert G.SIDE_LIBRARIES == (("klt", "_lib_klt"), ("mvs", "_lib_mvs"), ("selftest", "_lib_selftest"), ("fuse", "_lib_fuse"),
-                                ("patchmatch", "_lib_patchmatch"), ("tsdf", "_lib_tsdf"), ("raster", "_lib_raster"))
-    assert G.EVALUATION_LIBRARIES == (("nn", "_lib_nn"),) and G.REGISTRATION_LIBRARIES == (("icp", "_lib_icp"),)
     # one copy of the grid walk: the helpers stand in nn_grid.hpp and in neither .hip file
     nn = open(os.path.join(ROOT, "vggsfm_amd", "csrc", "nn", "nn.hip")).read()
     icp = open(os.path.join(ROOT, "vggsfm_amd", "csrc", "icp", "icp.hip")).read()
@@ -82,24 +49,6 @@ def test_header_table_and_library_agree():
                    "bool face_vertices(", "void closest_point("):
         assert shared.count(helper) == 1 and helper not in nn and helper not in icp, helper
     assert '#include "nn_grid.hpp"' in nn and '#include "../nn/nn_grid.hpp"' in icp
-
-
-def test_import_without_the_library_fails_loudly(tmp_path):
-    import shutil
-    pkg = tmp_path / "vggsfm_amd"
-    pkg.mkdir()
-    src = os.path.join(ROOT, "vggsfm_amd")
-    for name in ("_lib.py", "_lib_icp.py"):
-        shutil.copy(os.path.join(src, name), pkg / name)
-    (pkg / "__init__.py").write_text("")
-    code = ("import sys; sys.path.insert(0, sys.argv[1])\n"
-            "try:\n    import vggsfm_amd._lib_icp as T\n    T.lib()\nexcept RuntimeError as e:\n    print('RuntimeError:', e)\n"
-            "else:\n    print('loaded')\n")
-    out = subprocess.run([sys.executable, "-c", code, str(tmp_path)], capture_output=True, text=True, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.startswith("RuntimeError:") and "libvggsfm_amd_icp.so is missing" in out.stdout \
-        and "make -C vggsfm_amd/csrc/icp" in out.stdout and "no CPU or eager fallback" in out.stdout, out.stdout
-    assert "_L = I.lib()" in open(os.path.join(src, "registration.py")).read()          # the module loads it on import
 
 
 # --------------------------------------------------------------------------------------------------- refusals

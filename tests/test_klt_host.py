@@ -1,6 +1,6 @@
-"""CPU tests of the tracker: its C-ABI registry (vggsfm_amd/_lib_klt.py against csrc/klt/vggsfm_amd_klt.h and the dynamic
-symbols of libvggsfm_amd_klt.so), the yardstick of the GPU tests (the NumPy restatement of tests/klt_cases.py) against
-analytic truth, and the loud failure without the library.  No kernel is called here."""
+"""CPU tests of the tracker: what its C-ABI registry has of its own (the registry itself is tests/test_side_libraries.py's),
+the yardstick of the GPU tests (the NumPy restatement of tests/klt_cases.py) against analytic truth, and the loud failure of
+the product module without the library.  No kernel is called here."""
 import os
 import re
 import subprocess
@@ -10,33 +10,18 @@ import numpy as np
 import pytest
 
 from tests import klt_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_klt
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_klt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix; the main library and include/ know nothing of it."""
+    """What only the tracker has (tests/test_side_libraries.py compares table, header and symbols): two prototypes pinned by
+    hand, and the header's constants against the binding and the restatement."""
     header = open(_lib_klt.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_klt.SIGNATURES)
-    assert list(table) == list(functions) and len(functions) == 6 and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggk_"), name
+    functions, _ = _parse_header(header)
     assert functions["vggk_lk_track"][1][7] == "long" and functions["vggk_pyramid_floats"] == ("size_t", ["int"] * 3)
-    assert os.path.exists(_lib_klt.LIB_PATH), "run __graft_entry__.build() first"
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib_klt.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r" T (vgg[a-z]?_\w+)$", nm, flags=re.M)) == set(_lib_klt.SIGNATURES)
-    assert not set(_lib_klt.SIGNATURES) & set(_lib.SIGNATURES)
-    assert _lib_klt.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    L = _lib_klt.lib()
-    assert L.vggk_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_klt.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGK_(\w+) (\d+)", header))
     assert [int(consts[k]) for k in ("OK", "FLAT", "LEFT", "DIVERGED", "NONFINITE", "MAX_LEVELS", "MAX_RADIUS")] == \
         [_lib_klt.OK, _lib_klt.FLAT, _lib_klt.LEFT, _lib_klt.DIVERGED, _lib_klt.NONFINITE, _lib_klt.MAX_LEVELS,

@@ -1,91 +1,37 @@
-"""CPU tests of the meshing: its C-ABI registry (vggsfm_amd/_lib_tsdf.py against csrc/tsdf/vggsfm_amd_tsdf.h and the dynamic
-symbols of libvggsfm_amd_tsdf.so), what the entries refuse, the kernel's written-out case table against the one derived from
-the header's rule, the yardstick of the GPU tests (the NumPy restatement of tests/meshing_cases.py) on closed surfaces, on a
-volume with holes and against analytic truth, the margins of every decision the GPU tests compare exactly, the PLY
-round-trip, and the loud failure without the library.  No kernel is called here."""
-import os
+"""CPU tests of the meshing: what its C-ABI registry has of its own (the registry itself is tests/test_side_libraries.py's),
+what the entries refuse, the kernel's written-out case table against the one derived from the header's rule, the yardstick
+of the GPU tests (the NumPy restatement of tests/meshing_cases.py) on closed surfaces, on a volume with holes and against
+analytic truth, the margins of every decision the GPU tests compare exactly, and the PLY round-trip.  No kernel is called
+here."""
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import fusion_cases as FC
 from tests import meshing_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_fuse, _lib_klt, _lib_mvs, _lib_patchmatch, _lib_selftest, _lib_tsdf
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_tsdf
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHERS = (_lib, _lib_klt, _lib_mvs, _lib_selftest, _lib_fuse, _lib_patchmatch)
-
-
-def _symbols(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r" T (vgg[a-z]*_\w+)$", nm, flags=re.M))
+NAMES = ["vggv_build_arch", "vggv_case_table", "vggv_integrate", "vggv_mesh_count", "vggv_mesh_emit"]
 
 
 # --------------------------------------------------------------------------------------------------- registry
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix, disjoint from the other six libraries'; the header beside the source, not under include/."""
+    """What only the meshing has (tests/test_side_libraries.py compares table, header and symbols): the names and prototypes
+    pinned by hand, and the header's constants against the binding and the restatement."""
     header = open(_lib_tsdf.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_tsdf.SIGNATURES)
-    assert list(table) == list(functions) == ["vggv_build_arch", "vggv_case_table", "vggv_integrate", "vggv_mesh_count",
-                                              "vggv_mesh_emit"] and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggv_"), name
+    functions, _ = _parse_header(header)
+    assert list(_lib_tsdf.SIGNATURES) == list(functions) == NAMES
     assert functions["vggv_build_arch"] == ("pointer", [])
     assert functions["vggv_case_table"] == ("int", ["pointer"])
     assert functions["vggv_integrate"][1] == ["pointer"] * 5 + ["int"] * 3 + ["double"] * 4 + ["int"] * 3 + ["double"] + ["pointer"] * 4
     assert functions["vggv_mesh_count"][1] == ["pointer"] * 2 + ["int"] * 3 + ["double"] + ["pointer"] * 7
     assert functions["vggv_mesh_emit"][1] == ["pointer"] * 3 + ["double"] * 4 + ["int"] * 3 + ["double"] + ["pointer"] * 4 + \
         ["long"] * 2 + ["pointer"] * 5
-    assert os.path.exists(_lib_tsdf.LIB_PATH), "run __graft_entry__.build() first"
-    assert _symbols(_lib_tsdf.LIB_PATH) == set(_lib_tsdf.SIGNATURES)
-    prefixes = set()
-    for other in OTHERS:
-        assert not set(_lib_tsdf.SIGNATURES) & set(other.SIGNATURES)
-        prefixes |= {n[:n.index("_") + 1] for n in other.SIGNATURES}
-    assert "vggv_" not in prefixes and {"vgg_", "vggk_", "vggm_", "vggs_", "vggf_", "vggp_", "vggr_"} <= prefixes
-    assert _lib_tsdf.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_tsdf.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "tsdf")
-    L = _lib_tsdf.lib()
-    assert L.vggv_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_tsdf.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGV_(\w+) (\d+)", header))
     assert [int(consts[k]) for k in ("GROUP", "MAX_VIEWS")] == [_lib_tsdf.GROUP, _lib_tsdf.MAX_VIEWS] == [C.GROUP, 256]
     assert _lib_tsdf.MAX_NODES == (2 ** 31 - 1) // 7
-
-
-def test_the_other_libraries_keep_their_symbols():
-    """The meshing's translation unit is in none of the other six libraries: each exports exactly its table."""
-    for other in OTHERS:
-        assert _symbols(other.LIB_PATH) == set(other.SIGNATURES), other.LIB_PATH
-
-
-def test_import_without_the_library_fails_loudly(tmp_path):
-    """A copy of the package without libvggsfm_amd_tsdf.so: loading the table's library raises, naming the missing file and
-    the build command; there is no fallback."""
-    import shutil
-    pkg = tmp_path / "vggsfm_amd"
-    pkg.mkdir()
-    src = os.path.join(ROOT, "vggsfm_amd")
-    for name in ("_lib.py", "_lib_tsdf.py"):
-        shutil.copy(os.path.join(src, name), pkg / name)
-    (pkg / "__init__.py").write_text("")
-    code = ("import sys; sys.path.insert(0, sys.argv[1])\n"
-            "try:\n    import vggsfm_amd._lib_tsdf as T\n    T.lib()\nexcept RuntimeError as e:\n    print('RuntimeError:', e)\n"
-            "else:\n    print('loaded')\n")
-    out = subprocess.run([sys.executable, "-c", code, str(tmp_path)], capture_output=True, text=True, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.startswith("RuntimeError:") and "libvggsfm_amd_tsdf.so is missing" in out.stdout \
-        and "make -C vggsfm_amd/csrc/tsdf" in out.stdout and "no CPU or eager fallback" in out.stdout, out.stdout
-    assert "_L = T.lib()" in open(os.path.join(src, "meshing.py")).read()             # the module loads it on import
 
 
 # --------------------------------------------------------------------------------------------------- refusals

@@ -1,7 +1,7 @@
-"""CPU tests of the multi-view stereo: its C-ABI registry (vggsfm_amd/_lib_mvs.py against csrc/mvs/vggsfm_amd_mvs.h and the
-dynamic symbols of libvggsfm_amd_mvs.so), the yardstick of the GPU tests (the NumPy restatement of tests/mvs_cases.py)
-against analytic truth, the margins of every decision the GPU tests compare exactly, the host bookkeeping of
-vggsfm_amd/mvs.py, and the loud failure without the library.  No kernel is called here."""
+"""CPU tests of the multi-view stereo: what its C-ABI registry has of its own (the registry itself is
+tests/test_side_libraries.py's), the yardstick of the GPU tests (the NumPy restatement of tests/mvs_cases.py) against
+analytic truth, the margins of every decision the GPU tests compare exactly, the host bookkeeping of vggsfm_amd/mvs.py, and
+the loud failure of the product module without the library.  No kernel is called here."""
 import os
 import re
 import subprocess
@@ -11,46 +11,23 @@ import numpy as np
 import pytest
 
 from tests import mvs_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_klt, _lib_mvs
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_mvs
 from vggsfm_amd import pycolmap_compat as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix; three entries; the other two libraries and include/ know nothing of it."""
+    """What only the stereo has (tests/test_side_libraries.py compares table, header and symbols): prototypes pinned by
+    hand, and the header's constants against the binding and the restatement."""
     header = open(_lib_mvs.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_mvs.SIGNATURES)
-    assert list(table) == list(functions) and len(functions) == 3 and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggm_"), name
+    functions, _ = _parse_header(header)
     assert functions["vggm_plane_sweep"][1][8:12] == ["pointer", "int", "double", "double"]
     assert functions["vggm_consistency_filter"][1][4:6] == ["pointer", "int"] and functions["vggm_build_arch"] == ("pointer", [])
-    assert os.path.exists(_lib_mvs.LIB_PATH), "run __graft_entry__.build() first"
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib_mvs.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r" T (vgg[a-z]?_\w+)$", nm, flags=re.M)) == set(_lib_mvs.SIGNATURES)
-    assert not set(_lib_mvs.SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib_klt.SIGNATURES))
-    assert _lib_mvs.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_mvs.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "mvs")
-    L = _lib_mvs.lib()
-    assert L.vggm_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_mvs.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGM_(\w+) (\d+)", header))
     assert [int(consts[k]) for k in ("MAX_SOURCES", "MAX_PLANES", "MAX_RADIUS")] == \
         [_lib_mvs.MAX_SOURCES, _lib_mvs.MAX_PLANES, _lib_mvs.MAX_RADIUS] == [C.MAX_SOURCES, 1024, 3]
-
-
-def test_the_other_libraries_keep_their_symbols():
-    """The stereo's translation unit is in neither of the other two libraries (their Makefiles' wildcards do not descend)."""
-    for lib, table in ((_lib.LIB_PATH, _lib.SIGNATURES), (_lib_klt.LIB_PATH, _lib_klt.SIGNATURES)):
-        nm = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-        assert set(re.findall(r" T (vgg[a-z]?_\w+)$", nm, flags=re.M)) == set(table)
 
 
 def test_the_dense_stage_states_its_shared_code_once():

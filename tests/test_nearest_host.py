@@ -1,45 +1,32 @@
-"""CPU tests of the nearest-neighbour library: its C-ABI registry (vggsfm_amd/_lib_nn.py against csrc/nn/vggsfm_amd_nn.h and
-the dynamic symbols of libvggsfm_amd_nn.so), what the entries refuse, the yardstick of the GPU tests (the all-pairs NumPy
-restatement of tests/nearest_cases.py) against independent answers -- scipy's k-d tree, a dense minimisation over barycentric
-samples, the sphere's derived interval --, the kernel's candidate cells against the pairs the restatement accepts, the
-margins of every decision the GPU tests compare exactly, the metric formulas on a hand-computed example, and the loud
-failure without the library.  No kernel is called here."""
+"""CPU tests of the nearest-neighbour library: what its C-ABI registry has of its own (the registry itself is
+tests/test_side_libraries.py's), what the entries refuse, the yardstick of the GPU tests (the all-pairs NumPy restatement of
+tests/nearest_cases.py) against independent answers -- scipy's k-d tree, a dense minimisation over barycentric samples, the
+sphere's derived interval --, the kernel's candidate cells against the pairs the restatement accepts, the margins of every
+decision the GPU tests compare exactly, and the metric formulas on a hand-computed example.  No kernel is called here."""
 import math
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import nearest_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_fuse, _lib_klt, _lib_mvs, _lib_nn, _lib_patchmatch, _lib_raster, _lib_selftest, _lib_tsdf
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHERS = (_lib, _lib_klt, _lib_mvs, _lib_selftest, _lib_fuse, _lib_patchmatch, _lib_tsdf, _lib_raster)
 NAMES = ["vggn_build_arch", "vggn_point_cells", "vggn_gather_points", "vggn_cell_start", "vggn_nearest_point",
          "vggn_face_cell_counts", "vggn_face_cell_pairs", "vggn_nearest_face", "vggn_distance_stats"]
 GAP_FLOOR = 1e-12          # relative to r2; rounding differences would show at 1e-16
 
 
-def _symbols(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r" T (vgg[a-z]*_\w+)$", nm, flags=re.M))
-
-
 # --------------------------------------------------------------------------------------------------- registry
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix, disjoint from the other eight libraries'; the header beside the source, not under include/."""
+    """What only the search has (tests/test_side_libraries.py compares table, header and symbols): the names and prototypes
+    pinned by hand, and the header's constants against the binding and the restatement."""
     header = open(_lib_nn.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_nn.SIGNATURES)
-    assert list(table) == list(functions) == NAMES and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggn_"), name
+    functions, _ = _parse_header(header)
+    assert list(_lib_nn.SIGNATURES) == list(functions) == NAMES
     grid = ["double"] * 4 + ["int"] * 3
     assert functions["vggn_build_arch"] == ("pointer", [])
     assert functions["vggn_point_cells"] == ("int", ["pointer", "int"] + grid + ["pointer", "pointer"])
@@ -49,49 +36,16 @@ def test_header_table_and_library_agree():
     assert functions["vggn_nearest_face"][1] == ["pointer", "int", "pointer", "int", "pointer", "pointer", "int"] + grid + \
         ["pointer", "pointer", "int", "double", "double"] + ["pointer"] * 4
     assert functions["vggn_distance_stats"][1] == ["pointer", "int", "pointer", "int"] + ["pointer"] * 4
-    assert os.path.exists(_lib_nn.LIB_PATH), "run __graft_entry__.build() first"
-    assert _symbols(_lib_nn.LIB_PATH) == set(_lib_nn.SIGNATURES)
-    prefixes = set()
-    for other in OTHERS:
-        assert not set(_lib_nn.SIGNATURES) & set(other.SIGNATURES)
-        assert _symbols(other.LIB_PATH) == set(other.SIGNATURES), other.LIB_PATH       # and none of them took this unit in
-        prefixes |= {n[:n.index("_") + 1] for n in other.SIGNATURES}
-    assert "vggn_" not in prefixes and {"vgg_", "vggk_", "vggm_", "vggs_", "vggf_", "vggp_", "vggr_", "vggv_", "vggz_"} <= prefixes
-    for name in os.listdir(os.path.join(ROOT, "include")):
-        assert "vggn_" not in open(os.path.join(ROOT, "include", name)).read(), name
-    assert _lib_nn.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_nn.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "nn")
-    L = _lib_nn.lib()
-    assert L.vggn_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_nn.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = {k: int(v) for k, v in re.findall(r"#define VGGN_(\w+) (\d+)", header)}
     assert consts == dict(MAX_CELLS=_lib_nn.MAX_CELLS, MAX_THRESHOLDS=_lib_nn.MAX_THRESHOLDS, STATS_GROUPS=_lib_nn.STATS_GROUPS,
                           STATS_WORDS=_lib_nn.STATS_WORDS)
     assert consts["MAX_CELLS"] == 2 ** 25 and consts["MAX_THRESHOLDS"] == 8 and consts["STATS_GROUPS"] == C.STATS_GROUPS
-    import __graft_entry__ as G
-    assert G.SIDE_LIBRARIES[-1] == ("raster", "_lib_raster") and len(G.SIDE_LIBRARIES) == 7      # unchanged
-    assert G.EVALUATION_LIBRARIES == (("nn", "_lib_nn"),)
 
 
-def test_import_without_the_library_fails_loudly(tmp_path):
-    import shutil
-    pkg = tmp_path / "vggsfm_amd"
-    pkg.mkdir()
-    src = os.path.join(ROOT, "vggsfm_amd")
-    for name in ("_lib.py", "_lib_nn.py"):
-        shutil.copy(os.path.join(src, name), pkg / name)
-    (pkg / "__init__.py").write_text("")
-    code = ("import sys; sys.path.insert(0, sys.argv[1])\n"
-            "try:\n    import vggsfm_amd._lib_nn as T\n    T.lib()\nexcept RuntimeError as e:\n    print('RuntimeError:', e)\n"
-            "else:\n    print('loaded')\n")
-    out = subprocess.run([sys.executable, "-c", code, str(tmp_path)], capture_output=True, text=True, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.startswith("RuntimeError:") and "libvggsfm_amd_nn.so is missing" in out.stdout \
-        and "make -C vggsfm_amd/csrc/nn" in out.stdout and "no CPU or eager fallback" in out.stdout, out.stdout
-    assert "_L = N.lib()" in open(os.path.join(src, "nearest.py")).read()             # the module loads it on import
-    assert "torch.sum" not in open(os.path.join(src, "utils", "dense_metric.py")).read().split('"""', 2)[2]
+def test_the_dense_metrics_sum_on_the_device():
+    """No torch.sum below the docstring of utils/dense_metric.py: the counts and sums are vggn_distance_stats'."""
+    text = open(os.path.join(ROOT, "vggsfm_amd", "utils", "dense_metric.py")).read()
+    assert "torch.sum" not in text.split('"""', 2)[2]
 
 
 # --------------------------------------------------------------------------------------------------- refusals

@@ -1,90 +1,35 @@
-"""CPU tests of the PatchMatch refinement: its C-ABI registry (vggsfm_amd/_lib_patchmatch.py against
-csrc/patchmatch/vggsfm_amd_patchmatch.h and the dynamic symbols of libvggsfm_amd_pm.so), what the entries refuse, the hash,
-the yardstick of the GPU tests (the NumPy restatement of tests/patchmatch_cases.py) against analytic truth and against the
-sweep it starts from, the structure of a step, the margins of every decision the GPU tests compare exactly, and the loud
-failure without the library.  No kernel is called here."""
-import os
+"""CPU tests of the PatchMatch refinement: what its C-ABI registry has of its own (the registry itself is
+tests/test_side_libraries.py's), what the entries refuse, the hash, the yardstick of the GPU tests (the NumPy restatement of
+tests/patchmatch_cases.py) against analytic truth and against the sweep it starts from, the structure of a step, and the
+margins of every decision the GPU tests compare exactly.  No kernel is called here."""
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import patchmatch_cases as P
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_fuse, _lib_klt, _lib_mvs, _lib_patchmatch, _lib_selftest
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_patchmatch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHERS = (_lib, _lib_klt, _lib_mvs, _lib_selftest, _lib_fuse)
-
-
-def _symbols(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r" T (vgg[a-z]*_\w+)$", nm, flags=re.M))
+NAMES = ["vggr_build_arch", "vggr_plane_init", "vggr_plane_cost", "vggr_step", "vggr_outputs"]
 
 
 # --------------------------------------------------------------------------------------------------- registry
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix, disjoint from the other five libraries'; the header beside the source, not under include/."""
+    """What only the refinement has (tests/test_side_libraries.py compares table, header and symbols): the names and
+    prototypes pinned by hand, and the header's constants against the binding and the restatement."""
     header = open(_lib_patchmatch.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_patchmatch.SIGNATURES)
-    assert list(table) == list(functions) == ["vggr_build_arch", "vggr_plane_init", "vggr_plane_cost", "vggr_step",
-                                              "vggr_outputs"] and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggr_"), name
+    functions, _ = _parse_header(header)
+    assert list(_lib_patchmatch.SIGNATURES) == list(functions) == NAMES
     assert functions["vggr_build_arch"] == ("pointer", [])
     assert functions["vggr_plane_init"][1] == ["pointer"] * 4 + ["int"] * 4 + ["double"] * 3 + ["unsigned long long", "pointer", "pointer"]
     assert functions["vggr_plane_cost"][1] == ["pointer"] * 4 + ["int"] * 4 + ["pointer", "int", "int", "int", "double"] + ["pointer"] * 3
     assert functions["vggr_step"][1] == ["pointer"] * 4 + ["int"] * 4 + ["pointer", "int", "int", "int"] + ["double"] * 6 + \
         ["unsigned long long", "int", "int"] + ["pointer"] * 3
     assert functions["vggr_outputs"][1] == ["pointer"] * 4 + ["int"] * 4 + ["double"] + ["pointer"] * 4
-    assert os.path.exists(_lib_patchmatch.LIB_PATH), "run __graft_entry__.build() first"
-    assert _symbols(_lib_patchmatch.LIB_PATH) == set(_lib_patchmatch.SIGNATURES)
-    prefixes = set()
-    for other in OTHERS:
-        assert not set(_lib_patchmatch.SIGNATURES) & set(other.SIGNATURES)
-        prefixes |= {n[:n.index("_") + 1] for n in other.SIGNATURES}
-    assert "vggr_" not in prefixes and {"vgg_", "vggk_", "vggm_", "vggs_", "vggf_", "vggp_"} <= prefixes
-    assert _lib_patchmatch.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_patchmatch.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "patchmatch")
-    L = _lib_patchmatch.lib()
-    assert L.vggr_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_patchmatch.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGR_(\w+) (\d+)", header))
     assert [int(consts[k]) for k in ("MAX_SOURCES", "MAX_RADIUS")] == [_lib_patchmatch.MAX_SOURCES, _lib_patchmatch.MAX_RADIUS] \
-        == [P.MAX_SOURCES, P.MAX_RADIUS] == [_lib_mvs.MAX_SOURCES, _lib_mvs.MAX_RADIUS]
-
-
-def test_the_other_libraries_keep_their_symbols():
-    """The refinement's translation unit is in none of the other five libraries: each exports exactly its table."""
-    for other in OTHERS:
-        assert _symbols(other.LIB_PATH) == set(other.SIGNATURES), other.LIB_PATH
-
-
-def test_import_without_the_library_fails_loudly(tmp_path):
-    """A copy of the package without libvggsfm_amd_pm.so: loading the table's library raises, naming the missing file and
-    the build command; there is no fallback."""
-    import shutil
-    pkg = tmp_path / "vggsfm_amd"
-    pkg.mkdir()
-    src = os.path.join(ROOT, "vggsfm_amd")
-    for name in ("_lib.py", "_lib_patchmatch.py"):
-        shutil.copy(os.path.join(src, name), pkg / name)
-    (pkg / "__init__.py").write_text("")
-    code = ("import sys; sys.path.insert(0, sys.argv[1])\n"
-            "try:\n    import vggsfm_amd._lib_patchmatch as T\n    T.lib()\nexcept RuntimeError as e:\n    print('RuntimeError:', e)\n"
-            "else:\n    print('loaded')\n")
-    out = subprocess.run([sys.executable, "-c", code, str(tmp_path)], capture_output=True, text=True, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.startswith("RuntimeError:") and "libvggsfm_amd_pm.so is missing" in out.stdout \
-        and "make -C vggsfm_amd/csrc/patchmatch" in out.stdout and "no CPU or eager fallback" in out.stdout, out.stdout
-    assert "_L = PM.lib()" in open(os.path.join(src, "patchmatch.py")).read()        # the module loads it on import
+        == [P.MAX_SOURCES, P.MAX_RADIUS]                                            # (and the stereo's: test_side_libraries.py)
 
 
 # --------------------------------------------------------------------------------------------------- refusals

@@ -1,91 +1,36 @@
-"""CPU tests of the rasteriser: its C-ABI registry (vggsfm_amd/_lib_raster.py against csrc/raster/vggsfm_amd_raster.h and the
-dynamic symbols of libvggsfm_amd_raster.so), what the entries refuse, the yardstick of the GPU tests (the NumPy restatement
-of tests/render_cases.py, which tests every pixel against every face) against analytic truth, the candidate box the header
-gives the kernel against the pixels the restatement finds covered, the margins of every decision the GPU tests compare
-exactly, and the loud failure without the library.  No kernel is called here."""
-import os
+"""CPU tests of the rasteriser: what its C-ABI registry has of its own (the registry itself is tests/test_side_libraries.py's),
+what the entries refuse, the yardstick of the GPU tests (the NumPy restatement of tests/render_cases.py, which tests every
+pixel against every face) against analytic truth, the candidate box the header gives the kernel against the pixels the
+restatement finds covered, and the margins of every decision the GPU tests compare exactly.  No kernel is called here."""
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import meshing_cases as MC
 from tests import render_cases as C
-from tests.test_c_abi import _parse_header, _table_kinds
-from vggsfm_amd import _lib, _lib_fuse, _lib_klt, _lib_mvs, _lib_patchmatch, _lib_raster, _lib_selftest, _lib_tsdf
+from tests.test_c_abi import _parse_header
+from vggsfm_amd import _lib_raster
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHERS = (_lib, _lib_klt, _lib_mvs, _lib_selftest, _lib_fuse, _lib_patchmatch, _lib_tsdf)
 NAMES = ["vggz_build_arch", "vggz_raster", "vggz_resolve", "vggz_point_visibility"]
-
-
-def _symbols(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r" T (vgg[a-z]*_\w+)$", nm, flags=re.M))
 
 
 # --------------------------------------------------------------------------------------------------- registry
 def test_header_table_and_library_agree():
-    """The table's rows against the prototypes type by type, in the header's order; the library's dynamic symbols are the
-    table; one prefix, disjoint from the other seven libraries'; the header beside the source, not under include/."""
+    """What only the rasteriser has (tests/test_side_libraries.py compares table, header and symbols): the names and
+    prototypes pinned by hand, and the header's constants against the binding and the restatement."""
     header = open(_lib_raster.HEADER_PATH).read()
-    functions, structs = _parse_header(header)
-    table = _table_kinds(_lib_raster.SIGNATURES)
-    assert list(table) == list(functions) == NAMES and not structs
-    for name in functions:
-        assert table[name] == functions[name], name
-        assert name.startswith("vggz_"), name
+    functions, _ = _parse_header(header)
+    assert list(_lib_raster.SIGNATURES) == list(functions) == NAMES
     assert functions["vggz_build_arch"] == ("pointer", [])
     assert functions["vggz_raster"] == ("int", ["pointer", "int", "pointer", "int", "int"] + ["pointer"] * 4 + ["int"] * 4 +
                                         ["double", "pointer", "pointer"])
     assert functions["vggz_resolve"][1] == ["pointer", "pointer", "int", "pointer", "int"] + ["pointer"] * 5 + ["int"] * 4 + \
         ["pointer"] * 6
     assert functions["vggz_point_visibility"][1] == ["pointer", "int"] + ["pointer"] * 3 + ["int"] * 3 + ["double", "pointer", "pointer"]
-    assert os.path.exists(_lib_raster.LIB_PATH), "run __graft_entry__.build() first"
-    assert _symbols(_lib_raster.LIB_PATH) == set(_lib_raster.SIGNATURES)
-    prefixes = set()
-    for other in OTHERS:
-        assert not set(_lib_raster.SIGNATURES) & set(other.SIGNATURES)
-        prefixes |= {n[:n.index("_") + 1] for n in other.SIGNATURES}
-    assert "vggz_" not in prefixes and {"vgg_", "vggk_", "vggm_", "vggs_", "vggf_", "vggp_", "vggr_", "vggv_"} <= prefixes
-    assert _lib_raster.HEADER not in os.listdir(os.path.join(ROOT, "include"))
-    assert os.path.dirname(_lib_raster.HEADER_PATH) == os.path.join(ROOT, "vggsfm_amd", "csrc", "raster")
-    L = _lib_raster.lib()
-    assert L.vggz_build_arch() == b"gfx950"
-    for name, (restype, argtypes) in _lib_raster.SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     consts = dict(re.findall(r"#define VGGZ_(\w+) (\d+)", header))
     assert [int(consts[k]) for k in ("MAX_VIEWS", "SOLO_PIXELS")] == [_lib_raster.MAX_VIEWS, _lib_raster.SOLO_PIXELS] == \
         [256, C.SOLO_PIXELS]
-    import __graft_entry__ as G
-    assert G.SIDE_LIBRARIES[-1] == ("raster", "_lib_raster") and len(G.SIDE_LIBRARIES) == 7   # eight libraries with the main one
-
-
-def test_the_other_libraries_keep_their_symbols():
-    """The rasteriser's translation unit is in none of the other seven libraries: each exports exactly its table."""
-    for other in OTHERS:
-        assert _symbols(other.LIB_PATH) == set(other.SIGNATURES), other.LIB_PATH
-
-
-def test_import_without_the_library_fails_loudly(tmp_path):
-    import shutil
-    pkg = tmp_path / "vggsfm_amd"
-    pkg.mkdir()
-    src = os.path.join(ROOT, "vggsfm_amd")
-    for name in ("_lib.py", "_lib_raster.py"):
-        shutil.copy(os.path.join(src, name), pkg / name)
-    (pkg / "__init__.py").write_text("")
-    code = ("import sys; sys.path.insert(0, sys.argv[1])\n"
-            "try:\n    import vggsfm_amd._lib_raster as T\n    T.lib()\nexcept RuntimeError as e:\n    print('RuntimeError:', e)\n"
-            "else:\n    print('loaded')\n")
-    out = subprocess.run([sys.executable, "-c", code, str(tmp_path)], capture_output=True, text=True, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.startswith("RuntimeError:") and "libvggsfm_amd_raster.so is missing" in out.stdout \
-        and "make -C vggsfm_amd/csrc/raster" in out.stdout and "no CPU or eager fallback" in out.stdout, out.stdout
-    assert "_L = Z.lib()" in open(os.path.join(src, "render.py")).read()             # the module loads it on import
 
 
 # --------------------------------------------------------------------------------------------------- refusals

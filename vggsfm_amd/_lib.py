@@ -231,8 +231,14 @@ _side = {}
 
 
 def load_side_library(path, signatures, arch_entry, what, make_dir):
-    """Load the shared object of csrc/<make_dir> (a library and a table of its own, bound by a ``_lib_*`` module) or fail
-    loudly; loaded once per path."""
+    """Load the shared object of csrc/<make_dir> or fail loudly; loaded once per path.
+
+    The rule of the side libraries, stated here once: each has a shared object, a header beside its source and a ``_lib_*``
+    module with a table of its own, because the entries of every library, this one's included, are a closed, counted set
+    under one prefix.  The parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are this module's, and as here there
+    is NO fallback: a missing library or one built for another target raises.  A new one is a row of
+    ``__graft_entry__.SIDE_LIBRARIES``; tests/test_side_libraries.py compares every row's table with its header type by type
+    and with the library's symbols."""
     if path in _side:
         return _side[path]
     if not os.path.exists(path):

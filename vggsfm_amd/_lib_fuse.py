@@ -1,11 +1,5 @@
 """ctypes binding of vggsfm_amd/csrc/fuse/vggsfm_amd_fuse.h (libvggsfm_amd_fuse.so, built for gfx950): the entries of the
-depth-map fusion.
-
-A library and a table of their own, like the tracker's and the stereo's: the entries of the other libraries and the headers
-under include/ are closed, counted sets (tests/test_c_abi.py, tests/test_klt_host.py, tests/test_mvs_host.py).  The
-parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there, there is NO fallback: a missing
-library or one built for another target raises.  tests/test_fusion_host.py compares the table with the header type by type
-and with the library's symbols."""
+depth-map fusion.  A side library (``_lib.load_side_library``)."""
 import ctypes
 import os
 

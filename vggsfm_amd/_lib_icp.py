@@ -1,12 +1,7 @@
 """ctypes binding of vggsfm_amd/csrc/icp/vggsfm_amd_icp.h (libvggsfm_amd_icp.so, built for gfx950): the entries of the
 registration library -- the fused ICP step against a point grid or a triangle grid (transform, grid walk, residual, Jacobian
 row and the normal equations in one kernel), the sums of its workspace, the Gauss-Newton update of the device-resident
-transform, and the radius normals of a point grid.
-
-A library and a table of their own, like the other side libraries: the entries of the other libraries and the headers under
-include/ are closed, counted sets.  The parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as
-there, there is NO fallback: a missing library or one built for another target raises.  tests/test_icp_host.py compares the
-table with the header type by type and with the library's symbols."""
+transform, and the radius normals of a point grid.  A side library (``_lib.load_side_library``)."""
 import ctypes
 import os
 

@@ -1,9 +1,5 @@
 """ctypes binding of vggsfm_amd/csrc/klt/vggsfm_amd_klt.h (libvggsfm_amd_klt.so, built for gfx950): the tracker's entries.
-
-A library and a table of their own: the entries of libvggsfm_amd.so and the headers under include/ are a closed, counted set
-(tests/test_c_abi.py).  The parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there, there is
-NO fallback: a missing library or one built for another target raises.  tests/test_klt_host.py compares the table with the
-header type by type and with the library's symbols."""
+A side library (``_lib.load_side_library``)."""
 import ctypes
 import os
 

@@ -1,10 +1,5 @@
 """ctypes binding of vggsfm_amd/csrc/mvs/vggsfm_amd_mvs.h (libvggsfm_amd_mvs.so, built for gfx950): the entries of the
-plane-sweep multi-view stereo.
-
-A library and a table of their own, like the tracker's: the entries of libvggsfm_amd.so and the headers under include/ are a
-closed, counted set (tests/test_c_abi.py), and so are the tracker's (tests/test_klt_host.py).  The parameter types, ``check``,
-``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there, there is NO fallback: a missing library or one built for another
-target raises.  tests/test_mvs_host.py compares the table with the header type by type and with the library's symbols."""
+plane-sweep multi-view stereo.  A side library (``_lib.load_side_library``)."""
 import ctypes
 import os
 

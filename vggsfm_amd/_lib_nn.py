@@ -1,11 +1,7 @@
 """ctypes binding of vggsfm_amd/csrc/nn/vggsfm_amd_nn.h (libvggsfm_amd_nn.so, built for gfx950): the entries of the
 nearest-neighbour library -- the cells of points on a uniform grid, the grid's cell_start, the nearest point and the nearest
-triangle of the grid for many queries, and the counts and sums over such distances that the dense metrics are made of.
-
-A library and a table of their own, like the other side libraries: the entries of the other libraries and the headers under
-include/ are closed, counted sets.  The parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as
-there, there is NO fallback: a missing library or one built for another target raises.  tests/test_nearest_host.py compares
-the table with the header type by type and with the library's symbols."""
+triangle of the grid for many queries, and the counts and sums over such distances that the dense metrics are made of.  A
+side library (``_lib.load_side_library``)."""
 import ctypes
 import os
 

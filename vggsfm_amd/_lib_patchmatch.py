@@ -1,11 +1,5 @@
 """ctypes binding of vggsfm_amd/csrc/patchmatch/vggsfm_amd_patchmatch.h (libvggsfm_amd_pm.so, built for gfx950): the
-entries of the PatchMatch slanted-plane refinement of the multi-view stereo.
-
-A library and a table of their own, like the tracker's, the stereo's and the fusion's: the entries of the other libraries
-and the headers under include/ are closed, counted sets (tests/test_c_abi.py, tests/test_klt_host.py, tests/test_mvs_host.py,
-tests/test_fusion_host.py).  The parameter types, ``check``, ``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there,
-there is NO fallback: a missing library or one built for another target raises.  tests/test_patchmatch_host.py compares the
-table with the header type by type and with the library's symbols."""
+entries of the PatchMatch slanted-plane refinement of the multi-view stereo.  A side library (``_lib.load_side_library``)."""
 import ctypes
 import os
 

@@ -1,11 +1,7 @@
 """ctypes binding of vggsfm_amd/csrc/raster/vggsfm_amd_raster.h (libvggsfm_amd_raster.so, built for gfx950): the entries of
 the rasteriser -- a mesh drawn into the views of a reconstruction through a z-buffer of 64-bit keys, the buffer resolved to
-depth, face, normal and colour maps, and the visibility of points against depth maps.
-
-A library and a table of their own, like the tracker's, the stereo's, the fusion's, the refinement's and the meshing's: the
-entries of the other libraries and the headers under include/ are closed, counted sets.  The parameter types, ``check``,
-``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there, there is NO fallback: a missing library or one built for another
-target raises.  tests/test_render_host.py compares the table with the header type by type and with the library's symbols."""
+depth, face, normal and colour maps, and the visibility of points against depth maps.  A side library
+(``_lib.load_side_library``)."""
 import ctypes
 import os
 

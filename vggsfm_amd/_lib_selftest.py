@@ -1,8 +1,6 @@
 """ctypes binding of vggsfm_amd/csrc/selftest/vggsfm_amd_selftest.h (libvggsfm_amd_selftest.so, built for gfx950): entries
-that run the shared __device__ helpers of csrc/ on a caller's data, for the tests.
-
-A library and a table of their own, like the tracker's (``_lib_klt``): the parameter types, ``check`` and ``stream_ptr`` are
-``_lib``'s, and there is NO fallback: a missing library or one built for another target raises."""
+that run the shared __device__ helpers of csrc/ on a caller's data, for the tests.  A side library
+(``_lib.load_side_library``)."""
 import ctypes
 import os
 

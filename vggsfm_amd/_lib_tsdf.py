@@ -1,11 +1,6 @@
 """ctypes binding of vggsfm_amd/csrc/tsdf/vggsfm_amd_tsdf.h (libvggsfm_amd_tsdf.so, built for gfx950): the entries of the
-meshing -- TSDF integration of the depth maps and marching tetrahedra on the volume.
-
-A library and a table of their own, like the tracker's, the stereo's, the fusion's and the refinement's: the entries of the
-other libraries and the headers under include/ are closed, counted sets (tests/test_c_abi.py, tests/test_klt_host.py,
-tests/test_mvs_host.py, tests/test_fusion_host.py, tests/test_patchmatch_host.py).  The parameter types, ``check``,
-``stream_ptr`` and ``require_gpu`` are ``_lib``'s; as there, there is NO fallback: a missing library or one built for another
-target raises.  tests/test_meshing_host.py compares the table with the header type by type and with the library's symbols."""
+meshing -- TSDF integration of the depth maps and marching tetrahedra on the volume.  A side library
+(``_lib.load_side_library``)."""
 import ctypes
 import os
 
